@@ -3,14 +3,18 @@
 mask 0.75, bf16 MFMA, batch 128 per GPU, synthetic data, full optimizer steps (crop -> 2-view fwd -> 4 loss terms -> bwd ->
 grad all-reduce -> AdamW).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  `roofline` prices the whole step against the dense bf16 MFMA peak (118.80 GFLOP per
-image, fwd+bwd) and reports the dominant kernel (the MFMA GEMM family) timed with HIP events on its launch stream.
-`cpu_baseline` times the CPU oracle (oracle/, a validated restatement of the reference step) on the host cores — a reported
-baseline, never the thing being measured."""
+image, fwd+bwd).  A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the
+last timed step computed (DIR/<name>.npy, float32).  `--full` adds the measurements that cost runs or samplers of their own:
+the dominant kernel (the MFMA GEMM family) timed with HIP events on its launch stream (`roofline.dominant_kernel`), shader clock and
+board power over the timed region (`chip`), `cpu_baseline` (the CPU oracle — oracle/, a validated restatement of the reference step
+— timed on the host cores: a reported baseline, never the thing being measured) and, for N > 1, the line's data-parallel
+self-check and diagnosis (`data_parallel`)."""
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -190,6 +194,33 @@ def chip_info(device_index):
 
 
 SETTLE_STEPS = 10
+DUMP_SAMPLE = 1 << 22   # elements kept of an output larger than this (a fixed, seeded sample: 16 MB per array in float32)
+
+
+def sample_flat(t, seed):
+    """`t` flattened to float32 on the host; above DUMP_SAMPLE elements a fixed, seeded, sorted sample of it (same size -> same indices)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def step_outputs(model, loss, pred, mask):
+    """What the timed path hands its caller after its last step: the loss, the prediction and the mask the forward pass returned, and
+    the fp32 master weights the optimizer step left (sampled where large)."""
+    params = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    return {"loss": loss.detach().float().reshape(1).cpu().numpy(), "mask": mask.detach().float().cpu().numpy(),
+            "pred_sample": sample_flat(pred, 1), "params_sample": sample_flat(params, 2)}
+
+
+def dump_outputs(outdir, arrays):
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    log(f"wrote {', '.join(f'{n}.npy' for n in arrays)} ({sum(a.nbytes for a in arrays.values()) / 2 ** 20:.1f} MiB) to {outdir}")
 
 
 def main():
@@ -204,8 +235,11 @@ def main():
                     "N > 1 code path with several ranks on one GPU: set CSMAE_BENCH_ONE_GPU=1)")
     ap.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp8"], help="fp8: the blocks' forward / dX GEMMs on the fp8 MFMA path "
                     "(BASELINE.json configs[4]; use with --preset huge14).  The headline metric is defined in bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements: GEMM-family HIP-event timing, chip clock / power, "
+                    "the CPU oracle baseline, and for N > 1 the data-parallel self-check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU oracle baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: leave out the GEMM-family HIP-event timing pass")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -251,10 +285,10 @@ def main():
 
     def step():
         opt.zero_grad(set_to_none=True)
-        loss, _, _ = wrapped(samples, mask_ratio=0.75)
+        loss, pred, mask = wrapped(samples, mask_ratio=0.75)
         loss.backward()
         opt.step()
-        return loss
+        return loss, pred, mask
 
     # Initialisation, not measurement: the first ~8 steps of a process carry one-off costs (allocator growth, HIP signal / kernarg
     # pools, clock ramp) that showed up as a 70-100 ms stall somewhere in steps 5..10 when the queue runs unsynchronised.
@@ -263,7 +297,7 @@ def main():
     torch.cuda.synchronize()
     log(f"model built and settled ({SETTLE_STEPS} steps); warm-up {a.warmup} steps")
     for _ in range(a.warmup):
-        loss = step()
+        loss, _, _ = step()
     torch.cuda.synchronize()
     log("warm-up done; timing")
 
@@ -273,16 +307,21 @@ def main():
         torch.cuda.synchronize()
 
     fence()
-    watch = ChipWatch(local)
-    with watch:
+    watch = ChipWatch(local) if a.full else None
+    with watch if watch is not None else contextlib.nullcontext():
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            loss = step()
+            loss, pred, mask = step()
         fence()
         mine = time.perf_counter() - t0
+    # (pred / mask are views of the engine's workspace: read them before any further step)
+    outputs = step_outputs(model, loss, pred, mask) if (a.dump_outputs and rank == 0) else None
+    del pred, mask
     elapsed = torch.tensor([mine], device=device, dtype=torch.float64)
     dp_check = None
-    if world > 1:
+    if world > 1 and not a.full:
+        dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
+    if world > 1 and a.full:
         # self-verification of the N > 1 line (nobody can re-run it by hand): every rank really took part (all-reduce of ones), the
         # per-rank wall times (a straggler shows as max >> min), the loss each rank saw, and that the data-parallel replicas still hold
         # identical weights after the timed steps (the fp32 masters' checksum: max - min over ranks must be exactly 0)
@@ -336,8 +375,11 @@ def main():
     if not (final_loss == final_loss and abs(final_loss) < 1e30):
         raise SystemExit(f"non-finite loss {final_loss}")
 
+    if outputs is not None:
+        dump_outputs(a.dump_outputs, outputs)
+
     kernel = None
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         from csmae_hip.ops import KernelTimer
         with KernelTimer() as kt:
             step()
@@ -388,13 +430,13 @@ def main():
                        "loss": a.loss, "batch_per_gpu": a.batch, "global_batch": a.batch * world, "input": [chans, size, size], "parallelism": f"dp{world}",
                        "headline_config": bool(scale)},
             "loss": round(final_loss, 5), "library_source_sha256": csmae_hip.source_hash()[:16],
-            "chip": dict(chip_info(local), **watch.summary()),
+            "chip": dict(chip_info(local), **(watch.summary() if watch is not None else {})),
             "roofline": {"bound": "hbm" if hbm_floor_ms > mfma_floor_ms else "mfma", "hbm": hbm, "achieved": round(ach, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(ach / peak, 4),
                          "traffic": traffic if (a.preset == "base" and a.dtype == "bf16" and scale) else None, "algorithmic_gflop_per_image": gflop, "dominant_kernel": kernel},
         }
         if dp_check is not None:
             out["data_parallel"] = dp_check
-        if world == 1 and not a.no_cpu_baseline and a.preset == "base":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.preset == "base":
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

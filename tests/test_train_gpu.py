@@ -222,7 +222,7 @@ def test_bench_two_ranks_plumbing_on_one_gpu():
     env = dict(os.environ, CSMAE_BENCH_ONE_GPU="1")
     port = 29700 + os.getpid() % 200
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-kernel-timing"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-kernel-timing", "--full"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -242,6 +242,33 @@ def test_bench_two_ranks_plumbing_on_one_gpu():
     assert len(dp["bucket_allreduce"]) == dp["buckets_per_step"] and all(b["ms"] >= 0 and b["elements"] > 0 for b in dp["bucket_allreduce"])
     assert abs(dp["bucket_allreduce_ms_sum"] - sum(b["ms"] for b in dp["bucket_allreduce"])) < 1e-2
     assert dp["rccl_env"]["TORCH_NCCL_HIGH_PRIORITY"] == "1"
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run: the headline line without the `--full` measurements, exactly --steps timed steps, and
+    `--dump-outputs DIR` writing the last timed step's outputs as float32 .npy files (loss as in the line, mask, sampled prediction and
+    updated weights) within 64 MB."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "images/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["ms_per_step"] > 0 and abs(d["value"] - 8 / (d["ms_per_step"] / 1e3)) < 1e-2 * d["value"]
+    assert "cpu_baseline" not in d and "data_parallel" not in d and d["roofline"]["dominant_kernel"] is None and "clock_mhz_mean" not in d["chip"]
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["loss.npy", "mask.npy", "params_sample.npy", "pred_sample.npy"], files
+    arrs = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+    assert abs(float(arrs["loss"][0]) - d["loss"]) <= 1e-4 * max(1.0, abs(d["loss"]))
+    assert arrs["mask"].shape == (8, 196) and set(np.unique(arrs["mask"])) <= {0.0, 1.0} and int(arrs["mask"].sum()) == 8 * 147
+    assert arrs["pred_sample"].size == 8 * 196 * 768 and arrs["params_sample"].size > 0
 
 
 MICRO6 = dict(dim_model=128, encoder_num_layers=2, encoder_num_heads=2, decoder_embed_dim=64, decoder_num_layers=2, decoder_num_heads=2)
