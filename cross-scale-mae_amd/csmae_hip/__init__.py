@@ -14,6 +14,7 @@ import torch  # noqa: F401  -- must come first: libcsmae_hip.so has to bind to t
 F32, BF16 = 0, 1
 ABI_VERSION = 7
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_ATOMIC = 0, 1, 2, 3, 4
+ROUTE_F32, ROUTE_KSLAB = 7, 8   # csmae_gemm_route / csmae_gemm_ks_route codes beside the bf16 tile configurations 0..6
 LOSS_KINDS = {"mse": 0, "l2": 1, "mae": 2, "l1": 3, "bce": 4, "none": 5}
 # the ssim family: kind -> (per-patch kind, pyramid levels, weight of the ssim term)  MAE_ViT_Shared.py:165-267
 SSIM_KINDS = {"ssim": ("none", 1, 1.0), "ms_ssim": ("none", 5, 1.0), "mse_ssim": ("mse", 1, 0.1), "mse_ms_ssim": ("mse", 5, 0.1)}
@@ -39,6 +40,8 @@ _SIGNATURES = {
     "csmae_fp8_weights": [I, P, P, P, P, P, P, P],
     "csmae_gemm_fp8": [I, L, L, L, P, L, P, L, P, L, I, P, I, P, L, P, L, P, P, P, L, I, P, P, P, P],
     "csmae_gemm_force_tile": [I],
+    "csmae_gemm_route": [I, I, I, L, L, L, L, L, L, I, I],
+    "csmae_gemm_ks_route": [I, L, L, L, P, L, P, L, L, P, L, I],
     "csmae_attn_fwd": [I, L, I, I, I, P, P, P, P],
     "csmae_attn_bwd": [I, L, I, I, I, P, P, P, P, P, P],
     "csmae_attn_resident": [I, I, I],

@@ -139,6 +139,28 @@ def gemm(a, b, out, *, trans_a=False, trans_b=False, bias=None, epilogue=EPI_NON
     return out
 
 
+def gemm_route(a, b, out, *, trans_a=False, trans_b=False, epilogue=EPI_NONE, aux=None, splitk=1):
+    """The kernel gemm() would launch with these arguments (csmae_gemm_route, no launch): a bf16 tile configuration 0..6 or ROUTE_F32."""
+    K, M = (a.shape[0], a.shape[1]) if trans_a else (a.shape[1], a.shape[0])
+    N = b.shape[1] if trans_b else b.shape[0]
+    if aux is not None and aux.dtype == torch.uint8:
+        epilogue = {EPI_GELU: 6, EPI_DGELU: 7}[epilogue]
+    rc = load().csmae_gemm_route(dt(a), int(trans_a), int(trans_b), M, N, K, a.stride(0), b.stride(0), out.stride(0), epilogue, splitk)
+    check(min(rc, 0), "csmae_gemm_route")
+    return rc
+
+
+def gemm_ks_route(a, bk, b_plain, out, *, epilogue=EPI_NONE, aux=None):
+    """The kernel gemm_ks() would launch with these arguments (csmae_gemm_ks_route): ROUTE_KSLAB, or gemm_route() of its plain-weight fallback."""
+    M, K = a.shape
+    N = b_plain.shape[0]
+    if aux is not None and aux.dtype == torch.uint8:
+        epilogue = {EPI_GELU: 6, EPI_DGELU: 7}[epilogue]
+    rc = load().csmae_gemm_ks_route(dt(a), M, N, K, _p(a), a.stride(0), _p(bk), N, b_plain.stride(0), _p(out), out.stride(0), epilogue)
+    check(min(rc, 0), "csmae_gemm_ks_route")
+    return rc
+
+
 def gemm_ks(a, bk, b_plain, out, *, bias=None, epilogue=EPI_NONE, aux=None, resid=None, st=None):
     """out[M,N] = a[M,K] W^T (+ epilogue) with W [N,K] given twice: `bk` its K-slab mirror (flat bf16, Wk[K/32][N][32], weights_kslab) for the
     two-workgroups-per-CU kernel, `b_plain` in torch's layout for the shapes that kernel does not take."""

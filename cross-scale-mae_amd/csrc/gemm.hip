@@ -996,6 +996,37 @@ static bool k2_wanted(int mode, int epilogue, long long K, long long N, long lon
 bool gemm_k2_nn_wanted(int epilogue, long long K, long long N, long long M) { return k2_wanted(g_k2_nn, epilogue, K, N, M); }
 bool gemm_k2_nt_wanted(int epilogue, long long K, long long N, long long M) { return k2_wanted(g_k2_nt, epilogue, K, N, M); }
 
+// The kernel gemm_core launches for a problem (csmae_gemm_route answers with it): GEMM_ROUTE_F32 for fp32 operands, else the bf16 tile
+// configuration (0..6, as csmae_gemm_force_tile numbers them).  `epilogue` with the 8-bit gelu' forms already mapped to EPI_GELU / EPI_DGELU.
+static int gemm_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, int epilogue, int splitk) {
+  if (dtype != CSMAE_BF16) return GEMM_ROUTE_F32;
+  // tile choice: as large as keeps >= ~1.5 rounds of the 256 CUs busy (bytes staged per flop ~ 1/BM + 1/BN)
+  // tile choice (measured on the step's shapes, tools/gemm_bench.py): 256x256 wins whenever it fits, also when it leaves
+  // fewer tiles than CUs (N = 768 outputs: 150 tiles) because it halves the bytes staged per flop; 256x128 never won.
+  // 0: 128x128x32 (4 waves, 2 blocks/CU)   2: 256x256x32 (8 waves, 1 block/CU)   4: 256x256x64 software-pipelined (K-contiguous A)
+  int cfg = (M >= 256 && N >= 256) ? ((!transA || transB) ? 4 : 2) : 0;
+  if (cfg == 4 && !transA && splitk == 1) {  // 5: the same kernel with 192-row tiles, when it fills the CUs at least 10 % better
+    const long long t256 = (long long)cdiv(M, 256) * cdiv(N, 256), t192 = (long long)cdiv(M, 192) * cdiv(N, 256);
+    const long long c256 = cdiv(t256, 256) * 256, c192 = cdiv(t192, 256) * 192;
+    if (c192 * 10 <= c256 * 9) cfg = 5;
+  }
+  // 6: 128 x 256 tiles, two 4-wave workgroups per CU (k2_tile): K-contiguous A, K-strided B (dX products), whole 64-wide K steps; no ATOMIC
+  // epilogue (k2_tile has no accumulating store: it overwrote C with the product)
+  const bool k2_ok = !transA && transB && splitk == 1 && epilogue != EPI_ATOMIC && K % 64 == 0 && M >= 128 && N >= 256 && (M + 128) * lda * 2 < 0xFFFFFFF0ll && (K + 64) * ldb * 2 < 0xFFFFFFF0ll;
+  if (cfg >= 4 && k2_ok && gemm_k2_nn_wanted(epilogue, K, N, M)) cfg = 6;
+  if (g_force_cfg >= 0) cfg = g_force_cfg & 7;
+  if (cfg == 6 && !k2_ok) cfg = 4;
+  if (cfg > 6) cfg = 4;
+  if (cfg == 5 && (transA || splitk != 1)) cfg = 4;
+  if (cfg == 4 && transA && !transB) cfg = 2;  // (no 64-wide-K instantiation for K-strided A with K-contiguous B: unused by the step)
+  // the pipelined kernel fetches without per-piece predicates (k64_tile): K-contiguous operands need whole 64-wide K steps, and a byte offset up
+  // to one tile past the end of an operand must not wrap
+  if (cfg >= 4 && ((!(transA && transB) && K % 64 != 0) || ((transA ? K + 64 : M + 256) * lda * 2 >= 0xFFFFFFF0ll) || ((transB ? K + 64 : N + 256) * ldb * 2 >= 0xFFFFFFF0ll))) {
+    cfg = 2;
+  }
+  return cfg;
+}
+
 int gemm_core(int dtype, int transA, int transB, long long M, long long N, long long K,
                      const void* A, long long lda, const void* B, long long ldb,
                      void* C, long long ldc, int c_dtype, const float* bias, int epilogue,
@@ -1012,7 +1043,7 @@ int gemm_core(int dtype, int transA, int transB, long long M, long long N, long 
   CSMAE_REQUIRE(epilogue != EPI_RESID || (resid && ldr % 4 == 0), "csmae_gemm: residual epilogue needs resid");
   CSMAE_REQUIRE(splitk >= 1 && (splitk == 1 || epilogue == EPI_ATOMIC || epilogue == EPI_SPLIT), "csmae_gemm: split-K only with the accumulate epilogues");
   GemmArgs p;
-  p.force_cfg = g_force_cfg;
+  p.force_cfg = g_force_cfg < 0 ? 0 : g_force_cfg;   // (bits above 7: the kernels' tuning aids)
   p.split_stride = M * ldc;
   p.colsum = (epilogue == EPI_SPLIT && transA && transB && dtype == CSMAE_BF16) ? reinterpret_cast<float*>(aux) : nullptr;
   p.dq_a = p.dq_b = nullptr; p.a_fmt = 0; p.aux_q8 = q8; p.q_out = nullptr;
@@ -1038,32 +1069,8 @@ int gemm_core(int dtype, int transA, int transB, long long M, long long N, long 
     CSMAE_REQUIRE(abytes < 0xFFFFFFF0ll && bbytes < 0xFFFFFFF0ll, "csmae_gemm(bf16): operand larger than 4 GiB");
     p.a_bytes = (unsigned)abytes; p.b_bytes = (unsigned)bbytes;
     p.ktiles = cdiv(K, GEMM_BK);
-    // tile choice: as large as keeps >= ~1.5 rounds of the 256 CUs busy (bytes staged per flop ~ 1/BM + 1/BN)
-    // tile choice (measured on the step's shapes, tools/gemm_bench.py): 256x256 wins whenever it fits, also when it leaves
-    // fewer tiles than CUs (N = 768 outputs: 150 tiles) because it halves the bytes staged per flop; 256x128 never won.
-    // 0: 128x128x32 (4 waves, 2 blocks/CU)   2: 256x256x32 (8 waves, 1 block/CU)   4: 256x256x64 software-pipelined (K-contiguous A)
-    int cfg = (M >= 256 && N >= 256) ? ((!transA || transB) ? 4 : 2) : 0;
-    if (cfg == 4 && !transA && splitk == 1) {  // 5: the same kernel with 192-row tiles, when it fills the CUs at least 10 % better
-      const long long t256 = (long long)cdiv(M, 256) * cdiv(N, 256), t192 = (long long)cdiv(M, 192) * cdiv(N, 256);
-      const long long c256 = cdiv(t256, 256) * 256, c192 = cdiv(t192, 256) * 192;
-      if (c192 * 10 <= c256 * 9) cfg = 5;
-    }
-    int stg = 4;
-    // 6: 128 x 256 tiles, two 4-wave workgroups per CU (k2_tile): K-contiguous A, K-strided B (dX products), whole 64-wide K steps
-    const bool k2_ok = !transA && transB && splitk == 1 && K % 64 == 0 && M >= 128 && N >= 256 && (M + 128) * lda * 2 < 0xFFFFFFF0ll && (K + 64) * ldb * 2 < 0xFFFFFFF0ll;
-    if (cfg >= 4 && k2_ok && gemm_k2_nn_wanted(epilogue, K, N, M)) cfg = 6;
-    if (p.force_cfg >= 0) cfg = p.force_cfg & 7; else p.force_cfg = 0;
-    if (cfg == 6 && !k2_ok) cfg = 4;
-    if (cfg > 6) cfg = 4;
-    if (cfg == 5 && (transA || splitk != 1)) cfg = 4;
-    if (cfg == 4 && transA && !transB) cfg = 2;  // (no 64-wide-K instantiation for K-strided A with K-contiguous B: unused by the step)
-    // the pipelined kernel fetches without per-piece predicates (k64_tile): K-contiguous operands need whole 64-wide K steps, and a byte offset up
-    // to one tile past the end of an operand must not wrap
-    if (cfg >= 4 && ((!(transA && transB) && K % 64 != 0) || ((transA ? K + 64 : M + 256) * lda * 2 >= 0xFFFFFFF0ll) || ((transB ? K + 64 : N + 256) * ldb * 2 >= 0xFFFFFFF0ll))) {
-      cfg = 2;
-    }
+    const int cfg = gemm_route(dtype, transA, transB, M, N, K, lda, ldb, epilogue, splitk);
     if (cfg >= 4) p.ktiles = cdiv(K, 64);
-    (void)stg;
     const int bm = (cfg == 0 || cfg == 6) ? 128 : (cfg == 5 ? 192 : 256), bn = cfg >= 2 ? 256 : 128;
     p.tiles_m = cdiv(M, bm); p.tiles_n = cdiv(N, bn);
     p.ktiles_per_split = cdiv(p.ktiles, splitk);
@@ -1107,6 +1114,17 @@ extern "C" int csmae_gemm(int dtype, int transA, int transB, long long M, long l
                           void* aux, long long ldaux, const void* resid, long long ldr,
                           int splitk, void* stream) {
   return gemm_core(dtype, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, c_dtype, bias, epilogue, aux, ldaux, resid, ldr, splitk, stream);
+}
+
+// what csmae_gemm would launch (csmae_gemm_route; csmae_gemm_ks_route for its fallback): the epilogue as the caller passes it
+int gemm_core_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, int epilogue, int splitk) {
+  if (dtype != CSMAE_F32 && dtype != CSMAE_BF16) return CSMAE_ERR_UNSUPPORTED;
+  return gemm_route(dtype, transA, transB, M, N, K, lda, ldb, epilogue == 6 ? EPI_GELU : (epilogue == 7 ? EPI_DGELU : epilogue), splitk);
+}
+extern "C" int csmae_gemm_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, long long ldc,
+                                int epilogue, int splitk) {
+  (void)ldc;   // (no route depends on it today: part of the question so that callers need not change when one does)
+  return gemm_core_route(dtype, transA, transB, M, N, K, lda, ldb, epilogue, splitk);
 }
 
 // ------------------------------------------------------------------------------------ weight gradients

@@ -529,7 +529,11 @@ int gemm_k2_launch_dw(DwGroupArgs& ga, int count, int slots, float* workspace, l
 int gemm_force_cfg();                 // csmae_gemm_force_tile's value (-1 = heuristic)
 bool gemm_k2_nn_wanted(int epilogue, long long K, long long N, long long M);   // policy of csmae_gemm_k2_mode (gemm.hip)
 bool gemm_k2_nt_wanted(int epilogue, long long K, long long N, long long M);
-int gemm_k2_launch_nn(const GemmArgs& p, hipStream_t st);   // gemm_bf16_k2_kernel<true> (gemm_k2.hip)
+int gemm_k2_launch_nn(const GemmArgs& p, hipStream_t st);
+// route codes (csmae_gemm_route / csmae_gemm_ks_route, include/csmae.h): the bf16 tile configurations 0..6 of gemm_core, and
+#define GEMM_ROUTE_F32 7     // the fp32 kernel (gemm_f32_kernel)
+#define GEMM_ROUTE_KSLAB 8   // csmae_gemm_ks on the K-slab weight mirror (gemm_bf16_k2_kernel<false>)
+int gemm_core_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, int epilogue, int splitk);   // gemm_bf16_k2_kernel<true> (gemm_k2.hip)
 int gemm_core(int dtype, int transA, int transB, long long M, long long N, long long K, const void* A, long long lda, const void* B, long long ldb,
               void* C, long long ldc, int c_dtype, const float* bias, int epilogue, void* aux, long long ldaux, const void* resid, long long ldr,
               int splitk, void* stream);

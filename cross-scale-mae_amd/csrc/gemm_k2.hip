@@ -260,14 +260,23 @@ int gemm_k2_launch_nn(const GemmArgs& p0, hipStream_t st) {
 // ---- y = x W^T with W given as its K-slab mirror Wk[K/32][N][32] (csmae_weights_kslab): the forward products on the two-workgroups-per-CU
 // kernel (k2_tile).  `B_plain` ([N][K], ldb_plain) is the same weight in torch's layout: shapes the kernel does not take (K % 64, small M / N,
 // fp32 parity mode) go through csmae_gemm with it, so the caller never branches.
+// whether csmae_gemm_ks runs the K-slab kernel (true) or hands the product to csmae_gemm with the plain weight (csmae_gemm_ks_route asks the same)
+static bool ks_taken(int dtype, long long M, long long N, long long K, const void* A, long long lda, const void* Bk, long long slab_rows, const void* C, long long ldc,
+                     int epilogue) {
+  const int epi_kind = epilogue == 6 ? EPI_GELU : (epilogue == 7 ? EPI_DGELU : epilogue);
+  return dtype == CSMAE_BF16 && Bk && gemm_k2_nt_wanted(epi_kind, K, N, M) && (gemm_force_cfg() < 0 || (gemm_force_cfg() & 7) == 6) && K >= 64 && K % 64 == 0 && M >= 128 && N >= 256 && N % 4 == 0 && ldc % 4 == 0 && ldc >= N &&
+         lda % 8 == 0 && lda >= K && slab_rows >= N && slab_rows % 4 == 0 && (M + 128) * lda * 2 < 0xFFFFFFF0ll && (K / 32) * slab_rows * 64 < 0xFFFFFFF0ll &&
+         (((uintptr_t)A | (uintptr_t)Bk | (uintptr_t)C) & 15) == 0;
+}
+extern "C" int csmae_gemm_ks_route(int dtype, long long M, long long N, long long K, const void* A, long long lda, const void* Bk, long long slab_rows,
+                                   long long ldb_plain, const void* C, long long ldc, int epilogue) {
+  if (ks_taken(dtype, M, N, K, A, lda, Bk, slab_rows, C, ldc, epilogue)) return GEMM_ROUTE_KSLAB;
+  return gemm_core_route(dtype, 0, 0, M, N, K, lda, ldb_plain, epilogue, 1);
+}
 extern "C" int csmae_gemm_ks(int dtype, long long M, long long N, long long K, const void* A, long long lda, const void* Bk, long long slab_rows,
                              const void* B_plain, long long ldb_plain, void* C, long long ldc, int c_dtype, const float* bias, int epilogue,
                              void* aux, long long ldaux, const void* resid, long long ldr, void* stream) {
-  const int epi_kind = epilogue == 6 ? EPI_GELU : (epilogue == 7 ? EPI_DGELU : epilogue);
-  const bool ok = dtype == CSMAE_BF16 && Bk && gemm_k2_nt_wanted(epi_kind, K, N, M) && (gemm_force_cfg() < 0 || (gemm_force_cfg() & 7) == 6) && K >= 64 && K % 64 == 0 && M >= 128 && N >= 256 && N % 4 == 0 && ldc % 4 == 0 && ldc >= N &&
-                  lda % 8 == 0 && lda >= K && slab_rows >= N && slab_rows % 4 == 0 && (M + 128) * lda * 2 < 0xFFFFFFF0ll && (K / 32) * slab_rows * 64 < 0xFFFFFFF0ll &&
-                  (((uintptr_t)A | (uintptr_t)Bk | (uintptr_t)C) & 15) == 0;
-  if (!ok) {
+  if (!ks_taken(dtype, M, N, K, A, lda, Bk, slab_rows, C, ldc, epilogue)) {
     CSMAE_REQUIRE(B_plain != nullptr, "csmae_gemm_ks: shape not taken by the K-slab kernel and no plain weight given (M=%lld N=%lld K=%lld)", M, N, K);
     return gemm_core(dtype, 0, 0, M, N, K, A, lda, B_plain, ldb_plain, C, ldc, c_dtype, bias, epilogue, aux, ldaux, resid, ldr, 1, stream);
   }

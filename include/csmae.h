@@ -130,6 +130,17 @@ int csmae_gemm_fp8(int a_fmt, long long M, long long N, long long K, const void*
                    long long ldq, int q_fmt, const float* q_amax_prev /* [64] */, float* q_amax_next /* [64] */, float* q_dq, void* stream);
 /* tuning hook for tools/gemm_bench.py: force the bf16 block tile (0: 128x128, 1: 256x128, 2: 256x256, -1: heuristic) */
 int csmae_gemm_force_tile(int cfg);
+/* which kernel the next call with these arguments would launch (added within ABI version 7: no existing entry point changed; no launch): csmae_gemm_route for csmae_gemm — the bf16 tile
+ * configuration 0..6 (0: 128x128, 2: 256x256, 4: 256x256 pipelined, 5: 192x256 pipelined, 6: 128x256 two workgroups per CU; 1 / 3 only when
+ * forced) or CSMAE_GEMM_ROUTE_F32 —, csmae_gemm_ks_route for csmae_gemm_ks: CSMAE_GEMM_ROUTE_KSLAB, or the csmae_gemm route of its plain-weight
+ * fallback.  Both follow csmae_gemm_force_tile and csmae_gemm_k2_mode as they stand; the answer depends on pointers only through the
+ * alignment csmae_gemm_ks checks.  Negative: unsupported dtype. */
+#define CSMAE_GEMM_ROUTE_F32 7
+#define CSMAE_GEMM_ROUTE_KSLAB 8
+int csmae_gemm_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, long long ldc,
+                     int epilogue, int splitk);
+int csmae_gemm_ks_route(int dtype, long long M, long long N, long long K, const void* A, long long lda, const void* Bk, long long slab_rows,
+                        long long ldb_plain, const void* C, long long ldc, int epilogue);
 
 /* ---- softmax attention of timm Block (Attention.forward: softmax(q k^T * hd^-0.5) v), qkv is [B*T, 3*H*hd]
  * in timm's (3, H, hd) column order; out [B*T, H*hd]; lse [B, H, T] (natural log). */

@@ -1345,6 +1345,84 @@ def test_adamw_writes_the_kslab_mirrors(ops):
     assert float((lp[offs[0]:offs[0] + sizes[0]].float() - gp[offs[0]:offs[0] + sizes[0]]).abs().max()) < 1e-2
 
 
+def test_adamw_fp8_steps_and_writes_the_fp8_mirrors(ops):
+    """csmae_adamw_fp8 at the kernel level: three weights at non-zero flat offsets, the largest partial maximum of amax_prev in a non-zero slot,
+    one launch over all 64 x 64 tiles and, separately, two launches over halves of them.  p / m / v follow torch.optim.AdamW, p_lp is p rounded;
+    W8 is (p * (448 / amax_prev)).clamp(+-448) in e4m3fn from the kernel's own p, bit for bit, W8^T its transpose byte for byte; dq = amax_prev / 448
+    (an all-zero amax_prev: scale 1, dq 1); max(amax_next) = max |p|.  A non-finite gate leaves p, m, v, the mirrors and dq alone and carries the old
+    maximum into amax_next.  No byte of the mirrors outside the stepped weights moves."""
+    shapes, wd, lr, b1, b2, eps = [(64, 64), (128, 192), (320, 64)], 0.05, 1e-2, 0.9, 0.95, 1e-8
+    offs, off = [], 128
+    for N, K in shapes:
+        offs.append(off)
+        off += N * K + 64
+    total = off + 128
+    gen = torch.Generator().manual_seed(1400)
+    p0 = torch.randn(total, generator=gen) * 0.05
+    grads = [torch.randn(total, generator=gen) for _ in range(2)]
+    amax_prev = torch.zeros(len(shapes), 64)
+    for w, (o, (N, K)) in enumerate(zip(offs, shapes)):
+        if w < 2:   # partial maxima below the weight's maximum (some values saturate), the largest in slot 37
+            amax_prev[w] = torch.rand(64, generator=gen) * 0.5 * float(p0[o:o + N * K].abs().max())
+            amax_prev[w, 37] = 0.9 * float(p0[o:o + N * K].abs().max())
+    tiles = [[o, N, K, n0, k0, w] for w, (o, (N, K)) in enumerate(zip(offs, shapes)) for n0 in range(0, N, 64) for k0 in range(0, K, 64)]
+    tile8 = torch.tensor(tiles, dtype=torch.long, device="cuda")
+    half = len(tiles) // 2
+    ref = [p0[o:o + N * K].clone().requires_grad_(True) for o, (N, K) in zip(offs, shapes)]
+    opt = torch.optim.AdamW(ref, lr=lr, betas=(b1, b2), eps=eps, weight_decay=wd)
+
+    def state():
+        return dict(p=p0.cuda(), m=torch.zeros(total, device="cuda"), v=torch.zeros(total, device="cuda"),
+                    lp=torch.zeros(total, device="cuda", dtype=torch.bfloat16), w8=torch.full((total,), 0xA5, device="cuda", dtype=torch.uint8),
+                    w8t=torch.full((total,), 0xA5, device="cuda", dtype=torch.uint8), dq=torch.full((len(shapes),), -1.0, device="cuda"))
+
+    def step(s, k, parts, gate=None):
+        nxt = torch.zeros(len(shapes), 64, device="cuda")
+        for t8 in parts:
+            ops.adamw_fp8(t8, wd, s["p"], grads[k - 1].cuda(), s["m"], s["v"], lr, b1, b2, eps, k, s["lp"], gate, s["w8"], s["w8t"], amax_prev.cuda(), nxt, s["dq"])
+        return nxt
+
+    one, halves = state(), state()
+    for k in (1, 2):
+        for w, (o, (N, K)) in enumerate(zip(offs, shapes)):
+            ref[w].grad = grads[k - 1][o:o + N * K].clone()
+        opt.step()
+        nxt1 = step(one, k, [tile8])
+        nxt2 = step(halves, k, [tile8[:half], tile8[half:]])
+        for s, nxt in ((one, nxt1), (halves, nxt2)):
+            for w, (o, (N, K)) in enumerate(zip(offs, shapes)):
+                sl = slice(o, o + N * K)
+                assert_close(s["p"][sl], ref[w].detach(), 1e-6, 1e-7, f"adamw_fp8 p weight {w} step {k}")
+                st = opt.state[ref[w]]
+                # m = m + (1 - b1)(g - m), v = b2 v + (1 - b2) g^2 with 1 - b1 / 1 - b2 rounded in fp32 on the device (in double by torch): a few fp32
+                # ulps of the terms, element by element
+                gk = grads[k - 1][sl]
+                assert bool(((s["m"][sl].cpu() - st["exp_avg"]).abs() <= 2.0 ** -20 * (gk.abs() + st["exp_avg"].abs())).all()), f"adamw_fp8 m weight {w}"
+                assert bool(((s["v"][sl].cpu() - st["exp_avg_sq"]).abs() <= 2.0 ** -20 * (gk * gk + st["exp_avg_sq"])).all()), f"adamw_fp8 v weight {w}"
+                pk = s["p"][sl].cpu()
+                assert torch.equal(s["lp"][sl].cpu(), pk.to(torch.bfloat16)), f"p_lp weight {w}"
+                am = float(amax_prev[w].max())
+                scale = torch.tensor(448.0) / am if am > 0 else torch.tensor(1.0)
+                want = (pk * scale).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8).view(N, K)
+                assert torch.equal(s["w8"][sl].cpu().view(N, K), want), f"W8 weight {w}: {int((s['w8'][sl].cpu().view(N, K) != want).sum())} bytes differ"
+                assert torch.equal(s["w8t"][sl].cpu().view(K, N), want.t()), f"W8^T weight {w}"
+                assert float(s["dq"][w]) == (float(torch.tensor(am) / 448.0) if am > 0 else 1.0), (w, float(s["dq"][w]))
+                assert float(nxt[w].max()) == float(pk.abs().max()), (w, float(nxt[w].max()), float(pk.abs().max()))
+            keep = torch.ones(total, dtype=torch.bool)
+            for o, (N, K) in zip(offs, shapes):
+                keep[o:o + N * K] = False
+            assert bool((s["w8"].cpu()[keep] == 0xA5).all()) and bool((s["w8t"].cpu()[keep] == 0xA5).all()), "a mirror byte outside the weights moved"
+        for key in one:
+            assert torch.equal(one[key], halves[key]), f"one launch and two half launches differ in {key}"
+    # a tripped gate: nothing moves, the old maxima carry over
+    before = {k: v.clone() for k, v in one.items()}
+    nxt = step(one, 2, [tile8], gate=torch.tensor([float("inf")], device="cuda"))
+    for key in before:
+        assert torch.equal(one[key], before[key]), f"a non-finite gate changed {key}"
+    for w in range(len(shapes)):
+        assert float(nxt[w].max()) == float(amax_prev[w].max()), (w, float(nxt[w].max()))
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_colsum_and_cast(ops, dtype):
     x = rnd(1237, 200, seed=110).to(dtype)
