@@ -15,10 +15,13 @@ F32, BF16 = 0, 1
 ABI_VERSION = 7
 EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_ATOMIC = 0, 1, 2, 3, 4
 ROUTE_F32, ROUTE_KSLAB = 7, 8   # csmae_gemm_route / csmae_gemm_ks_route codes beside the bf16 tile configurations 0..6
+ATTN_ROUTE_RESIDENT, ATTN_ROUTE_STREAM, ATTN_ROUTE_ANY, ATTN_ROUTE_F32 = 0, 1, 2, 3   # csmae_attn_route
+ATTN_STREAM_OWN, ATTN_STREAM_TILE = 128, 64   # rows a streaming-attention workgroup owns / rows of one streamed tile (csrc/attention_common.h)
 LOSS_KINDS = {"mse": 0, "l2": 1, "mae": 2, "l1": 3, "bce": 4, "none": 5}
 # the ssim family: kind -> (per-patch kind, pyramid levels, weight of the ssim term)  MAE_ViT_Shared.py:165-267
 SSIM_KINDS = {"ssim": ("none", 1, 1.0), "ms_ssim": ("none", 5, 1.0), "mse_ssim": ("mse", 1, 0.1), "mse_ms_ssim": ("mse", 5, 0.1)}
 
+_ADDED_WITHIN_ABI = ("csmae_attn_route", "csmae_attn_stream_mode")   # additions that left ABI_VERSION alone (see load())
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSMAE_LIB_PATH") or os.path.join(_HERE, "libcsmae_hip.so")   # (override: A/B builds of tools/)
 
@@ -45,6 +48,8 @@ _SIGNATURES = {
     "csmae_attn_fwd": [I, L, I, I, I, P, P, P, P],
     "csmae_attn_bwd": [I, L, I, I, I, P, P, P, P, P, P],
     "csmae_attn_resident": [I, I, I],
+    "csmae_attn_route": [I, I, I],
+    "csmae_attn_stream_mode": [I],
     "csmae_attn_fwd_q": [I, L, I, I, I, P, P, P, P, I, P, P, P, P],
     "csmae_attn_bwd_q": [I, L, I, I, I, P, P, P, P, P, P, I, P, P, P, P],
     "csmae_layernorm_fwd": [I, I, L, I, P, P, P, F, P, P, P, P, P, I, P, P, P, P],
@@ -134,7 +139,13 @@ def load():
     lib.csmae_source_hash.restype = ctypes.c_char_p
     lib.csmae_abi_version.restype = c_int
     for name, sig in _SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:
+            # an A/B library built from an older revision (CSMAE_LIB_PATH, tools/build_rev.sh) lacks the entry points added within this ABI
+            # version: it still loads, and calling one of them raises AttributeError.  The package's own library must export everything.
+            if name in _ADDED_WITHIN_ABI and os.environ.get("CSMAE_LIB_PATH"):
+                continue
+            raise CsmaeError(f"{LIB_PATH} does not export {name}: rebuild it with `make`")
         fn.argtypes = sig
         fn.restype = c_int
     if lib.csmae_abi_version() != ABI_VERSION:

@@ -352,6 +352,21 @@ def attn_resident(dtype_code, T, hd):
     return load().csmae_attn_resident(dtype_code, T, hd) == 1
 
 
+def attn_route(dtype_code, T, hd):
+    """The kernel family attn_fwd() / attn_bwd() would run for (dtype, T, head_dim) under the current attn_stream_mode (csmae_attn_route, no launch):
+    ATTN_ROUTE_RESIDENT, ATTN_ROUTE_STREAM, ATTN_ROUTE_ANY or ATTN_ROUTE_F32; raises for an unsupported dtype or geometry."""
+    rc = load().csmae_attn_route(dtype_code, T, hd)
+    if rc < 0:
+        raise RuntimeError(f"csmae_attn_route: dtype {dtype_code}, T {T}, head_dim {hd} unsupported ({rc})")
+    return rc
+
+
+def attn_stream_mode(mode=-1):
+    """Set which bf16 shapes take the streaming MFMA attention kernels — 0: none (the scalar any-length kernels run what is not LDS-resident), 1: what
+    is not resident (default), 2: every shape with head_dim % 8 == 0 — and return the previous mode; any other value only queries."""
+    return load().csmae_attn_stream_mode(mode)
+
+
 def attn_fwd(qkv, out, lse, B, T, H, hd, emit=None, st=None):
     """emit = (q_out uint8 [B*T, H*hd], fmt, amax_prev [64], amax_next [64], dq [1]): also write `out` as fp8 bytes for attn.proj's GEMM."""
     if emit is None:

@@ -9,70 +9,8 @@
 // Backward = a query-row pass (dQ) and a key-column pass (dK, dV) that mirror the forward; S and dP are
 // recomputed in each pass (attention is 3.7 % of the step's FLOPs; this avoids cross-wave reductions).
 // fp32 path: exact fp32 (parity mode), one thread per query row / key column.
-#include "common.h"
+#include "attention_common.h"
 #include <cstdlib>
-
-#define LOG2E 1.4426950408889634f
-#define LN2 0.6931471805599453f
-
-// ------------------------------------------------------------------------------------------ bf16 helpers
-template <int HD> struct AttnLds { static constexpr int STRIDE = (HD + 8) * 2; };  // bytes per row (16-B multiple)
-
-// stage rows [0,TP) of one head's matrix (column offset `col0` inside a [B*T, ld] tensor) into LDS, zero padded
-template <int HD, int TP>
-__device__ __forceinline__ void stage_head(char* dst, const bf16_t* src, long long row0, int ld, int col0, int T, int hd) {
-  constexpr int CH = HD / 8;
-  for (int e = threadIdx.x; e < TP * CH; e += blockDim.x) {
-    int r = e / CH, c = e - r * CH;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (r < T && c * 8 < hd) v = *reinterpret_cast<const uint4*>(src + (row0 + r) * ld + col0 + c * 8);
-    *reinterpret_cast<uint4*>(dst + r * AttnLds<HD>::STRIDE + c * 16) = v;
-  }
-}
-
-// The same for several matrices at once, with every global load issued before the first LDS store.  stage_head() called three or
-// four times in a row ran ~3.5 dependent load->store iterations per matrix: ~10 exposed memory latencies (~10 of the ~18 us a
-// workgroup lives) before any arithmetic could start.
-template <int HD, int TP, int NT, int NM>
-struct HeadStager {
-  static constexpr int CH = HD / 8, IT = (TP * CH + NT - 1) / NT;
-  uint4 v[NM][IT];
-  __device__ __forceinline__ void load(int m, const bf16_t* src, long long row0, int ld, int col0, int T, int hd) {
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-      const int e = threadIdx.x + i * NT, r = e / CH, c = e - r * CH;
-      v[m][i] = make_uint4(0, 0, 0, 0);
-      if (e < TP * CH && r < T && c * 8 < hd) v[m][i] = *reinterpret_cast<const uint4*>(src + (row0 + r) * ld + col0 + c * 8);
-    }
-  }
-  __device__ __forceinline__ void store(int m, char* dst) {
-#pragma unroll
-    for (int i = 0; i < IT; ++i) {
-      const int e = threadIdx.x + i * NT, r = e / CH, c = e - r * CH;
-      if (e < TP * CH) *reinterpret_cast<uint4*>(dst + r * AttnLds<HD>::STRIDE + c * 16) = v[m][i];
-    }
-  }
-};
-
-// K-contiguous fragment (lane (t,g): row = row0 + t, elements d = ks*32 + 8g .. +8)
-template <int HD>
-__device__ __forceinline__ s8_t frag_rows(const char* img, int row0, int ks, int t, int g) {
-  return *reinterpret_cast<const s8_t*>(img + (row0 + t) * AttnLds<HD>::STRIDE + (ks * 32 + 8 * g) * 2);
-}
-// transposed fragment via tr-read: A operand with i = column (c0 + t) and k = rows {r0+4g+j, r0+16+4g+j}
-template <int HD>
-__device__ __forceinline__ s8_t frag_cols_tr(const char* img, int r0, int c0, int t, int g) {
-  const char* p = img + (r0 + 4 * g + (t >> 2)) * AttnLds<HD>::STRIDE + (c0 + (t & 3) * 4) * 2;
-  s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s4_t, p));
-  s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s4_t, p + 16 * AttnLds<HD>::STRIDE));
-  return join_s4(lo, hi);
-}
-__device__ __forceinline__ s8_t pack_pair(f4_t a, f4_t b) {
-  unsigned u0 = pack2bf(a[0], a[1]), u1 = pack2bf(a[2], a[3]), u2 = pack2bf(b[0], b[1]), u3 = pack2bf(b[2], b[3]);
-  uint4 u = make_uint4(u0, u1, u2, u3);
-  return __builtin_bit_cast(s8_t, u);
-}
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8_t, a), __builtin_bit_cast(bf8_t, b), c, 0, 0, 0)
 
 // ------------------------------------------------------------------------------------------ bf16 forward
 // With 32-wide heads two neighbouring heads share every 128-B line of a qkv row.  Workgroups are dealt to the 8 XCDs round-robin,
@@ -813,11 +751,13 @@ __global__ __launch_bounds__(256) void attn_bwd_f32(const float* __restrict__ qk
 }
 
 // ------------------------------------------------------------------------------------------ any length (fallback)
-// Sequences that do not fit the LDS-resident kernels above (`--input_size 320` and up: T > 288; the reference accepts any
-// --input_size / --patch_size, main_pretrain.py:70-86; fp32 parity mode from T (hd + 1) 16 B > 160 KiB).  Same arithmetic as the fp32
-// kernels — one thread per query row / key column, fp32 accumulation, exact softmax — with K, V, Q and dO rows read from global memory
-// (every thread of a wave reads the same row: one transaction per load) and only the per-row statistics in LDS.  Outside the surveyed
-// geometries (T <= 257), so correctness — not speed — is what it is for: ~10-30x slower than the MFMA kernels per FLOP.
+// What neither MFMA family takes (attn_route below): bf16 heads whose head_dim is a multiple of 4 but not of 8 (the 16-byte operand
+// chunks of the MFMA kernels do not divide them), fp32 parity mode from T (hd + 1) 16 B > 160 KiB or head_dim > 96, and — only with
+// csmae_attn_stream_mode(0), the routing before the streaming family existed — every bf16 sequence that is not LDS-resident.  The
+// reference accepts any --input_size / --patch_size (main_pretrain.py:70-86); long bf16 sequences with head_dim % 8 == 0 run
+// attention_stream.hip.  Same arithmetic as the fp32 kernels — one thread per query row / key column, fp32 accumulation, exact softmax —
+// with K, V, Q and dO rows read from global memory (every thread of a wave reads the same row: one transaction per load) and only the
+// per-row statistics in LDS.  Correctness — not speed — is what it is for: ~10-30x slower than the MFMA kernels per FLOP.
 template <typename T, int HD>
 __global__ __launch_bounds__(256) void attn_fwd_any(const T* __restrict__ qkv, T* __restrict__ out, float* __restrict__ lse, int Tn, int H, int D, int hd, float scale) {
   const int b = blockIdx.y / H, h = blockIdx.y - b * H;
@@ -966,8 +906,32 @@ static void launch_bwd_bf16(int BH, const void* qkv, const void* out, const void
   else if (hd <= 64) { NKF_SMALL(64, CALL) else { CALL(64, 14); } }                    \
   else { NKF_SMALL(96, CALL) }
 
-// (T, head_dim) pairs the LDS-resident MFMA kernels cover; anything else with head_dim <= 128, T <= 8192 runs the any-length kernels
+// (T, head_dim) pairs the LDS-resident MFMA kernels cover; anything else with head_dim <= 128, T <= 8192 runs the streaming kernels or the any-length ones (attn_route)
 static bool bf16_resident(int T, int hd) { return hd % 8 == 0 && T <= 288 && (hd <= 32 || (hd <= 64 && T <= 224) || (hd <= 96 && T <= 96)); }
+// ---- one routing decision for csmae_attn_fwd, csmae_attn_bwd and csmae_attn_route.  csmae_attn_stream_mode: 0 never stream (the routing before
+// the streaming family: A/B runs), 1 stream what is not resident (default), 2 stream every bf16 shape with head_dim % 8 == 0, resident ones too
+// (tests, A/B).  The fp8-emitting entry points (csmae_attn_*_q) always take the resident kernels.
+enum { ATTN_ROUTE_RESIDENT = 0, ATTN_ROUTE_STREAM = 1, ATTN_ROUTE_ANY = 2, ATTN_ROUTE_F32 = 3 };
+static int initial_stream_mode() {            // CSMAE_DEBUG=attn_stream=0|1|2 presets the mode for programs that never call the switch (bench.py A/B)
+  const char* v = csmae_debug_opt("attn_stream");
+  return v && v[0] >= '0' && v[0] <= '2' && !v[1] ? v[0] - '0' : 1;
+}
+static int g_attn_stream_mode = initial_stream_mode();
+static int attn_route(int dtype, int T, int hd, bool emit) {
+  if (dtype == CSMAE_F32) return ATTN_ROUTE_F32;
+  if (dtype != CSMAE_BF16) return CSMAE_ERR_UNSUPPORTED;
+  if (T <= 0 || T > 8192 || hd <= 0 || hd > 128 || hd % 4 != 0) return CSMAE_ERR_ARG;   // (what check_common refuses)
+  const bool streamable = hd % 8 == 0 && !emit;
+  if (g_attn_stream_mode == 2 && streamable) return ATTN_ROUTE_STREAM;
+  if (bf16_resident(T, hd)) return ATTN_ROUTE_RESIDENT;
+  return g_attn_stream_mode == 1 && streamable ? ATTN_ROUTE_STREAM : ATTN_ROUTE_ANY;
+}
+extern "C" int csmae_attn_route(int dtype, int T, int hd) { return attn_route(dtype, T, hd, false); }
+extern "C" int csmae_attn_stream_mode(int mode) {
+  const int prev = g_attn_stream_mode;
+  if (mode >= 0 && mode <= 2) g_attn_stream_mode = mode;
+  return prev;
+}
 static int check_common(const char* who, long long B, int T, int H, int D, int hd) {
   CSMAE_REQUIRE(B > 0 && T > 0 && H > 0 && hd > 0 && D == H * hd, "%s: bad geometry B=%lld T=%d H=%d D=%d hd=%d", who, B, T, H, D, hd);
   CSMAE_REQUIRE(hd <= 128 && hd % 4 == 0 && T <= 8192 && B * H <= 0x7fffffffll, "%s: head_dim %d (multiple of 4, <= 128) / sequence length %d (<= 8192) unsupported", who, hd, T);
@@ -982,7 +946,9 @@ static int attn_fwd_impl(int dtype, long long B, int T, int H, int hd, const voi
   const float scale = 1.0f / sqrtf((float)hd);
   const int BH = (int)(B * H);
   if (dtype == CSMAE_BF16) {
-    if (!bf16_resident(T, hd)) { CSMAE_REQUIRE(!em, "csmae_attn_fwd_q: the fp8 copy is emitted by the LDS-resident kernels only (csmae_attn_resident)"); launch_any<bf16_t>(false, B, T, H, D, hd, scale, qkv, nullptr, nullptr, lse, nullptr, out, st); return csmae_check_launch("csmae_attn_fwd"); }
+    const int route = attn_route(dtype, T, hd, em != nullptr);
+    if (route == ATTN_ROUTE_STREAM) { if (int rs = attn_stream_fwd(B, T, H, hd, qkv, out, lse, st)) return rs; return csmae_check_launch("csmae_attn_fwd"); }
+    if (route != ATTN_ROUTE_RESIDENT) { CSMAE_REQUIRE(!em, "csmae_attn_fwd_q: the fp8 copy is emitted by the LDS-resident kernels only (csmae_attn_resident)"); launch_any<bf16_t>(false, B, T, H, D, hd, scale, qkv, nullptr, nullptr, lse, nullptr, out, st); return csmae_check_launch("csmae_attn_fwd"); }
 #define CALLF(HDV, NK) launch_fwd_bf16<HDV, NK>(BH, qkv, out, lse, T, H, D, hd, scale, st, em)
     DISPATCH_BF16(CALLF)
 #undef CALLF
@@ -1025,7 +991,9 @@ static int attn_bwd_impl(int dtype, long long B, int T, int H, int hd, const voi
   const float scale = 1.0f / sqrtf((float)hd);
   const int BH = (int)(B * H);
   if (dtype == CSMAE_BF16) {
-    if (!bf16_resident(T, hd)) { CSMAE_REQUIRE(!em, "csmae_attn_bwd_q: the fp8 copy is emitted by the LDS-resident kernels only (csmae_attn_resident)"); launch_any<bf16_t>(true, B, T, H, D, hd, scale, qkv, out, dout, nullptr, lse, dqkv, st); return csmae_check_launch("csmae_attn_bwd"); }
+    const int route = attn_route(dtype, T, hd, em != nullptr);
+    if (route == ATTN_ROUTE_STREAM) { if (int rs = attn_stream_bwd(B, T, H, hd, qkv, out, dout, lse, dqkv, st)) return rs; return csmae_check_launch("csmae_attn_bwd"); }
+    if (route != ATTN_ROUTE_RESIDENT) { CSMAE_REQUIRE(!em, "csmae_attn_bwd_q: the fp8 copy is emitted by the LDS-resident kernels only (csmae_attn_resident)"); launch_any<bf16_t>(true, B, T, H, D, hd, scale, qkv, out, dout, nullptr, lse, dqkv, st); return csmae_check_launch("csmae_attn_bwd"); }
 #define CALLB(HDV, NK) launch_bwd_bf16<HDV, NK>(BH, qkv, out, dout, lse, dqkv, T, H, D, hd, scale, st, em)
     DISPATCH_BF16(CALLB)
 #undef CALLB

@@ -147,6 +147,20 @@ int csmae_gemm_ks_route(int dtype, long long M, long long N, long long K, const 
 int csmae_attn_fwd(int dtype, long long B, int T, int H, int hd, const void* qkv, void* out, float* lse, void* stream);
 int csmae_attn_bwd(int dtype, long long B, int T, int H, int hd, const void* qkv, const void* out, const void* dout,
                    const float* lse, void* dqkv, void* stream);
+/* which kernel family the next csmae_attn_fwd / csmae_attn_bwd call with these arguments runs (added within ABI version 7: no existing entry point
+ * changed; no launch): CSMAE_ATTN_ROUTE_RESIDENT — bf16 MFMA kernels with the whole K and V of a (sample, head) in LDS (the shapes csmae_attn_resident
+ * lists) —, CSMAE_ATTN_ROUTE_STREAM — bf16 MFMA kernels that stream K / V (Q / dO) tiles, online softmax: any T <= 8192, head_dim % 8 == 0,
+ * head_dim <= 128 —, CSMAE_ATTN_ROUTE_ANY — the scalar any-length kernels — or CSMAE_ATTN_ROUTE_F32 (fp32 parity mode).  Negative: unsupported dtype
+ * or geometry.  Same reference expression for every route (timm Attention.forward inside Block, models_mae/MAE_ViT_Baseline.py:160-188).
+ * csmae_attn_stream_mode(mode) sets the choice and returns the previous mode: 0 never stream (the routing before the streaming kernels: A/B runs),
+ * 1 stream what is not resident (default), 2 stream every bf16 shape with head_dim % 8 == 0, resident ones too (tests, A/B); any other value only
+ * queries.  csmae_attn_resident and the fp8-emitting csmae_attn_*_q entry points do not depend on it. */
+#define CSMAE_ATTN_ROUTE_RESIDENT 0
+#define CSMAE_ATTN_ROUTE_STREAM 1
+#define CSMAE_ATTN_ROUTE_ANY 2
+#define CSMAE_ATTN_ROUTE_F32 3
+int csmae_attn_route(int dtype, int T, int hd);
+int csmae_attn_stream_mode(int mode);
 /* fp8 mode (BASELINE configs[4]): the same two kernels also leave their output as OCP fp8 bytes for the nn.Linear that consumes it —
  * attn.proj forward reads `out` (q_fmt 0: e4m3), attn.qkv's backward reads dqkv (q_fmt 1: e5m2) — quantised from the rounded bf16 values
  * with FMAX / max(q_amax_prev[64]) (the tensor's amax one step earlier: delayed scaling, conventions of csmae_gemm_fp8); q_amax_next[64]
