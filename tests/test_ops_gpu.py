@@ -1146,6 +1146,50 @@ def test_recon_loss_bf16_predictions(ops, kind, norm_pix, C):
         assert torch.equal(rl_v, rowloss[N * L:])
 
 
+@pytest.mark.parametrize("kind", ["mse", "l1", "bce"])
+@pytest.mark.parametrize("norm_pix", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_recon_loss_pad_columns_and_small_patches(ops, kind, norm_pix, dtype):
+    """Rows wider than a patch (P = 48 of a 56-element row, the pad NaN) and a patch shorter than a wave: the generic kernels read only
+    the first P columns, and the backward zeroes the pad columns and the cls rows.  Tolerances of the two tests above."""
+    import csmae_oracle as O
+    N, C, S, p = 2, 3, 16, 4
+    L, P, LD = 16, 48, 56
+    B2 = 2 * N
+    img0, img1 = rnd(N, C, S, S, seed=84), rnd(N, C, S, S, seed=85)
+    pred_full = rnd(B2 * (L + 1), P, seed=86).to(dtype).float()
+    mask = (torch.rand(B2, L, generator=torch.Generator().manual_seed(87)) > 0.3).float()
+    mask[0, 0] = 1.0
+    pr = pred_full.clone().requires_grad_(True)
+    pv = pr.reshape(B2, L + 1, P)[:, 1:]
+    lo = O.loss_fn(kind, O.recon_target(img0, p, C, norm_pix), pv[:N], mask[:N])
+    lc = O.loss_fn(kind, O.recon_target(img1, p, C, norm_pix), pv[N:], mask[N:])
+    g = 0.7
+    ((lo + lc) * g).backward()
+    mm = None
+    if kind == "bce":
+        mm = torch.empty(4, device="cuda")
+        ops.target_minmax(dev(img0), dev(img1), torch.empty(B2 * L * 2, device="cuda"), mm, B2, N, C, S, p, norm_pix)
+    gp = torch.full((B2 * (L + 1), LD), float("nan"), device="cuda", dtype=dtype)
+    gp[:, :P] = dev(pred_full, dtype)
+    gm = dev(mask)
+    for use_mask in (True, False):
+        rowloss = torch.full((B2 * L,), float("nan"), device="cuda")
+        ops.recon_loss_fwd(kind, norm_pix, dev(img0), dev(img1), gp, mm, rowloss, B2, N, C, S, p, mask=gm if use_mask else None)
+        losses = torch.zeros(8, device="cuda")
+        ops.loss_finalize(N * L, 2, rowloss, gm, 1.0, losses)
+        assert_close(losses[1:3], torch.stack([lo, lc]), 2e-5, 1e-6, f"recon {kind} padded rows")
+    gout = torch.tensor([g], device="cuda")
+    dpred = torch.full((B2 * (L + 1), LD), float("nan"), device="cuda", dtype=dtype)
+    ops.recon_loss_bwd(kind, norm_pix, dev(img0), dev(img1), gp, mm, gm, losses, gout, 1.0, dpred, B2, N, C, S, p)
+    if dtype == torch.float32:
+        assert_close(dpred[:, :P], pr.grad, 1e-4, 1e-7, f"dpred {kind}")
+    else:
+        assert_close(dpred[:, :P].float(), pr.grad, 2 ** -8, 1e-7, f"dpred {kind} bf16")     # (one bf16 rounding of the fp32 value)
+    assert bool((dpred[:, P:] == 0).all()), "pad columns"
+    assert bool((dpred.reshape(B2, L + 1, LD)[:, 0] == 0).all()), "cls rows"
+
+
 def _ssim_run(ops, kind, norm_pix, img0, img1, pred_rows, mask, p, g=0.7, vscale=1.0):
     """Two views through csmae_ssim_fwd / loss_finalize / ssim_apply / ssim_bwd / recon_loss_bwd -> (losses[8], dpred rows)."""
     from csmae_hip import SSIM_KINDS
@@ -1172,10 +1216,12 @@ def _ssim_run(ops, kind, norm_pix, img0, img1, pred_rows, mask, p, g=0.7, vscale
 
 
 @pytest.mark.parametrize("kind,S,p,norm_pix", [("ssim", 64, 16, False), ("mse_ssim", 64, 16, True), ("ssim", 48, 8, False),
-                                               ("ms_ssim", 176, 16, False), ("mse_ms_ssim", 168, 8, False), ("ms_ssim", 200, 8, True)])
+                                               ("ms_ssim", 176, 16, False), ("mse_ms_ssim", 168, 8, False), ("ms_ssim", 200, 8, True),
+                                               ("ssim", 40, 8, True)])
 def test_ssim_family_fwd_bwd(ops, kind, S, p, norm_pix):
     """MAE_ViT_Shared.forward_loss_{ssim,ms_ssim,mse_ssim,mse_ms_ssim} (:165-267), two views, against the oracle's
-    autograd.  200 / 8 -> 25 patches per side: levels 200, 100, 50, 25 (odd: padded pooling), 13.  Tolerance: fp32, 1e-4 on the
+    autograd.  200 / 8 -> 25 patches per side: levels 200, 100, 50, 25 (odd: padded pooling), 13.  40 / 8: 30 window positions, one
+    partial 32-pixel tile in the forward and 2 x 2 partial tiles in the backward.  Tolerance: fp32, 1e-4 on the
     loss; the gradient within 2e-3 of its largest element (E[x^2] - mu^2 cancellations, different summation order)."""
     import csmae_oracle as O
     N, C = 2, 3
@@ -1278,6 +1324,41 @@ def test_ntxent_vs_reference_golden(ops, bs):
     lp = torch.empty(2 * bs * 3, D, device="cuda", dtype=torch.bfloat16)
     ops.latent_grad_finish(dlat, dpool, 0.5, lp, 2 * bs, 3)
     want = torch.stack([torch.zeros_like(ref), ref * 0.5, ref * 0.5], dim=1).reshape(-1, D)
+    assert_close(dlat, want, 2e-3, 1e-6 + 1e-3 * ref.abs().max().item(), "latent grad finish")
+    assert_close(lp, want, 2e-2, 1e-6 + 1e-2 * ref.abs().max().item(), "latent grad lp")
+
+
+@pytest.mark.parametrize("geom", [(2, 3, 2, 6), (3, 4, 3, 10), (5, 3, 2, 33)])
+def test_ntxent_generic_route(ops, geom):
+    """D % 4 != 0: the one-column-per-thread pool and backward kernels and the scalar branch of the similarity kernel, against the
+    oracle in float64 on the kept-token means.  Tolerances of test_ntxent_vs_reference_golden.  latent_grad_finish takes 16-byte columns
+    only, so it sees the generic route's dpool zero-padded to the next multiple of four."""
+    import csmae_oracle as O
+    N, Te, keep, D = geom
+    latent = rnd(2 * N, Te, D, seed=92)
+    f = latent[:, 1:1 + keep].double().mean(1).requires_grad_(True)
+    loss = O.ntxent(f[:N], f[N:])
+    loss.backward()
+    ref = f.grad.float()
+    z, inv = torch.empty(2 * N, D, device="cuda"), torch.empty(2 * N, device="cuda")
+    E, neg, rl = torch.empty(2 * N, 2 * N, device="cuda"), torch.empty(2 * N, device="cuda"), torch.empty(2 * N, device="cuda")
+    ops.ntxent_fwd(dev(latent), z, inv, E, neg, rl, N, Te, keep)
+    losses = torch.zeros(8, device="cuda")
+    ops.loss_finalize(4, 1, torch.zeros(4, device="cuda"), torch.ones(4, device="cuda"), 1.0, losses, ce_rowloss=rl, ce_rows=2 * N)
+    assert_close(losses[4], loss.detach().float(), 1e-5, 1e-6, f"ntxent {geom}")
+    gout = torch.tensor([1.0], device="cuda")
+    dpool = torch.full((2 * N, D), float("nan"), device="cuda")
+    ops.ntxent_bwd(z, inv, E, neg, gout, dpool, N)
+    assert_close(dpool, ref, 2e-3, 1e-6 + 1e-3 * ref.abs().max().item(), "ntxent grad")
+    Dp = (D + 3) // 4 * 4
+    dpool4 = torch.zeros(2 * N, Dp, device="cuda")
+    dpool4[:, :D] = dpool
+    dlat = torch.zeros(2 * N * Te, Dp, device="cuda")
+    lp = torch.empty(2 * N * Te, Dp, device="cuda", dtype=torch.bfloat16)
+    ops.latent_grad_finish(dlat, dpool4, 1.0 / keep, lp, 2 * N, Te)
+    want = torch.zeros(2 * N, Te, Dp)
+    want[:, 1:, :D] = (ref / keep)[:, None]
+    want = want.reshape(-1, Dp)
     assert_close(dlat, want, 2e-3, 1e-6 + 1e-3 * ref.abs().max().item(), "latent grad finish")
     assert_close(lp, want, 2e-2, 1e-6 + 1e-2 * ref.abs().max().item(), "latent grad lp")
 
