@@ -21,7 +21,8 @@ LOSS_KINDS = {"mse": 0, "l2": 1, "mae": 2, "l1": 3, "bce": 4, "none": 5}
 # the ssim family: kind -> (per-patch kind, pyramid levels, weight of the ssim term)  MAE_ViT_Shared.py:165-267
 SSIM_KINDS = {"ssim": ("none", 1, 1.0), "ms_ssim": ("none", 5, 1.0), "mse_ssim": ("mse", 1, 0.1), "mse_ms_ssim": ("mse", 5, 0.1)}
 
-_ADDED_WITHIN_ABI = ("csmae_attn_route", "csmae_attn_stream_mode")   # additions that left ABI_VERSION alone (see load())
+_ADDED_WITHIN_ABI = ("csmae_attn_route", "csmae_attn_stream_mode", "csmae_probe_pool_fwd", "csmae_bn1d_fwd", "csmae_head_linear_fwd",
+                     "csmae_head_linear_bwd", "csmae_softmax_ce", "csmae_lars_step")   # additions that left ABI_VERSION alone (see load())
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSMAE_LIB_PATH") or os.path.join(_HERE, "libcsmae_hip.so")   # (override: A/B builds of tools/)
 
@@ -93,6 +94,12 @@ _SIGNATURES = {
     "csmae_cast_f32_to_bf16": [L, P, P, P],
     "csmae_cast_bf16_to_f32": [L, P, P, P],
     "csmae_colsum": [I, L, I, P, L, P, P],
+    "csmae_probe_pool_fwd": [I, I, L, I, I, P, P, P, F, P, P],
+    "csmae_bn1d_fwd": [L, I, P, F, F, P, P, P, P, I, P],
+    "csmae_head_linear_fwd": [L, I, I, P, P, P, P, P],
+    "csmae_head_linear_bwd": [L, I, I, P, P, P, P, P, I, P],
+    "csmae_softmax_ce": [L, I, P, P, P, P, P, P, P, I, P],
+    "csmae_lars_step": [I, P, F, F, F, F, P, P, P],
     "csmae_stream_create_cu_mask": [I, P, P],
     "csmae_stream_destroy": [P],
 }

@@ -1089,6 +1089,17 @@ class Engine:
     def encode(self, imgs: torch.Tensor, mask_ratio: float, noise: torch.Tensor):
         """`forward_encoder` of the reference (MAE_ViT_Baseline.py:243-266) for a single-view engine: patch-embed the kept patches,
         pos-embed, cls, encoder blocks (encoder_norm's output is discarded there).  -> latent [N, keep+1, D], mask, ids_restore."""
+        ws = self.encode_stream(imgs, mask_ratio, noise)
+        c, st = self.cfg, self.st
+        lat = ws.enc["x"][c["Ne"]]
+        if ws.lat32 is not None:
+            ops.cast_f32(lat, ws.lat32, st=st)
+            lat = ws.lat32
+        return lat.view(imgs.shape[0], ws.Te, c["D"]).clone(), ws.mask.clone(), ws.ids_restore.clone()
+
+    def encode_stream(self, imgs: torch.Tensor, mask_ratio: float, noise: torch.Tensor):
+        """The encoder half of `encode`, leaving its result where the blocks wrote it: the workspace whose `enc["x"][Ne]` [N * (keep+1), D] is
+        the residual stream behind the last block (fp32, or bf16 in throughput mode) — valid until the engine's next pass."""
         assert self.views == 1, "encode()/decode() run on a single-view (Baseline-variant) engine"
         c = self.cfg
         N = imgs.shape[0]
@@ -1112,11 +1123,7 @@ class Engine:
         ops.embed_assemble(ws.tok, P("encoder_pos_embed").view(L + 1, D), P("cls_token").view(D), ws.ids_keep, ws.enc["x"][0], N, keep, st=st)
         for i in range(c["Ne"]):
             self._block_fwd(ws.enc, i, f"encoder.{i}.", ws.Me, D, c["He"], N, ws.Te)
-        lat = ws.enc["x"][c["Ne"]]
-        if ws.lat32 is not None:
-            ops.cast_f32(lat, ws.lat32, st=st)
-            lat = ws.lat32
-        return lat.view(N, ws.Te, D).clone(), ws.mask.clone(), ws.ids_restore.clone()
+        return ws
 
     def decode(self, latent: torch.Tensor, ids_restore: torch.Tensor):
         """`forward_decoder` (MAE_ViT_Baseline.py:268-297): decoder_embed, mask-token fill + unshuffle + pos-embed, decoder blocks,

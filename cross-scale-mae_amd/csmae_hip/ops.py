@@ -619,4 +619,83 @@ def colsum(x, out, st=None):
     check(load().csmae_colsum(dt(x), x.shape[0], x.shape[1], _p(x), x.stride(0), _p(out), st if st is not None else stream()), "csmae_colsum")
 
 
+# ---- linear probing (csrc/linprobe.hip): everything behind the last transformer block, fp32
+def _f32c(*ts):
+    for t in ts:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), "linear-probe kernels take contiguous fp32 tensors"
+
+
+def probe_pool_fwd(x, gamma, beta, feat, global_pool, eps=1e-6, st=None):
+    """feat [N, D] = LayerNorm(mean of tokens 1.. of x [N, T, D]) (global_pool) or LayerNorm(x[:, 0]); x fp32 or bf16."""
+    N, T, D = x.shape
+    assert x.is_contiguous() and feat.shape == (N, D) and gamma.numel() == D and beta.numel() == D
+    _f32c(gamma, beta, feat)
+    check(load().csmae_probe_pool_fwd(dt(x), int(bool(global_pool)), N, T, D, _p(x), _p(gamma), _p(beta), float(eps), _p(feat),
+                                      st if st is not None else stream()), "csmae_probe_pool_fwd")
+    return feat
+
+
+def bn1d_fwd(feat, fbn, running_mean, running_var, nbt=None, eps=1e-6, momentum=0.1, training=True, st=None):
+    """BatchNorm1d(D, affine=False) over the batch axis of feat [N, D]; training moves the running statistics in place."""
+    N, D = feat.shape
+    if training and N == 1:   # (torch.nn.functional.batch_norm's refusal, before anything is launched)
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(feat.shape)}")
+    assert fbn.shape == feat.shape and running_mean.numel() == D and running_var.numel() == D and (nbt is None or nbt.dtype == torch.int64)
+    _f32c(feat, fbn, running_mean, running_var)
+    check(load().csmae_bn1d_fwd(N, D, _p(feat), float(eps), float(momentum), _p(fbn), _p(running_mean), _p(running_var), _p(nbt), int(bool(training)),
+                                st if st is not None else stream()), "csmae_bn1d_fwd")
+    return fbn
+
+
+def head_linear_fwd(x, w, b, logits, st=None):
+    """logits [N, K] = x [N, D] w[K, D]^T + b."""
+    (N, D), K = x.shape, w.shape[0]
+    assert w.shape == (K, D) and logits.shape == (N, K) and (b is None or b.numel() == K)
+    _f32c(x, w, b, logits)
+    check(load().csmae_head_linear_fwd(N, D, K, _p(x), _p(w), _p(b), _p(logits), st if st is not None else stream()), "csmae_head_linear_fwd")
+    return logits
+
+
+def head_linear_bwd(dlogits, x, dw, db=None, accumulate=False, gscale=None, st=None):
+    """dw [K, D] (+)= gscale dlogits^T x, db [K] (+)= gscale sum_n dlogits (gscale: device scalar or None)."""
+    (N, K), D = dlogits.shape, x.shape[1]
+    assert x.shape == (N, D) and dw.shape == (K, D) and (db is None or db.numel() == K)
+    _f32c(dlogits, x, dw, db, gscale)
+    check(load().csmae_head_linear_bwd(N, D, K, _p(dlogits), _p(x), _p(gscale), _p(dw), _p(db), int(bool(accumulate)),
+                                       st if st is not None else stream()), "csmae_head_linear_bwd")
+
+
+def softmax_ce(logits, labels, loss, dlogits=None, counts=None, gout=None, accumulate_counts=False, scratch=None, st=None):
+    """loss[0] = mean cross-entropy; dlogits = gout (softmax - onehot) / N; counts [2] (+)= top-1 / top-5 hits.  labels int64 [N]."""
+    N, K = logits.shape
+    assert labels.dtype == torch.int64 and labels.numel() == N and labels.is_contiguous() and (dlogits is None or dlogits.shape == logits.shape)
+    _f32c(logits, loss, dlogits, counts, gout)
+    if scratch is None:
+        scratch = torch.empty(3 * N, device=logits.device, dtype=torch.float32)
+    assert scratch.numel() >= 3 * N
+    check(load().csmae_softmax_ce(N, K, _p(logits), _p(labels), _p(gout), _p(scratch), _p(loss), _p(dlogits), _p(counts), int(bool(accumulate_counts)),
+                                  st if st is not None else stream()), "csmae_softmax_ce")
+
+
+LARS_NORM_FLOATS = 128   # scratch floats per tensor of a csmae_lars_step launch
+
+
+def lars_table(params, grads, mus):
+    """Device table of csmae_lars_step: one row {p, g, mu addresses, numel, ndim > 1} per tensor (contiguous fp32 on the GPU)."""
+    rows = []
+    for p, g, mu in zip(params, grads, mus):
+        _f32c(p, g, mu)
+        assert g.shape == p.shape and mu.shape == p.shape
+        rows.append([_p(p), _p(g), _p(mu), p.numel(), int(p.dim() > 1)])
+    return torch.tensor(rows, dtype=torch.int64).to(params[0].device)
+
+
+def lars_step(table, norms, lr, weight_decay, momentum, trust_coefficient, gate=None, st=None):
+    n = table.shape[0]
+    assert table.dtype == torch.int64 and table.shape[1] == 5 and table.is_contiguous() and norms.numel() >= n * LARS_NORM_FLOATS
+    _f32c(norms, gate)
+    check(load().csmae_lars_step(n, _p(table), float(lr), float(weight_decay), float(momentum), float(trust_coefficient), _p(norms), _p(gate),
+                                 st if st is not None else stream()), "csmae_lars_step")
+
+
 __all__ = [n for n in dir() if not n.startswith("_")]

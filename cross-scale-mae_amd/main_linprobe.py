@@ -1,0 +1,253 @@
+#!/usr/bin/env python3
+"""Linear probing of a pre-trained encoder on the MI355X path — the reference's `main_linprobe.py` flags that make sense here (same
+names, types and defaults), its model factory call, LR scaling, probe head (BatchNorm1d(affine=False) + Linear, everything else frozen,
+:515-525), LARS, checkpoint layout and `log.jsonl`, and a `train_one_epoch` / `evaluate` pair after `engine_finetune.py`.
+
+Differences:
+  * `--dataset_type synthetic` (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches with fixed labels generated on the
+    device; the fMoW / Sentinel / EuroSAT readers of `util/datasets.py` need rasterio / fiona and are not wired (selecting them raises);
+  * `--model` defaults to `vit_base_patch16` (the reference's default `mae_vit_base` names no factory of `models_vit`);
+    `--embed_dim / --depth / --num_heads` override a factory's geometry for small runs;
+  * the per-iteration loss and the top-1 / top-5 hit counts stay on the device and are drained every `--print_freq` iterations; a
+    non-finite loss raises at that drain, and LARS skips on the device every update whose loss was not finite;
+  * the probe head is always built (the reference builds it only with --finetune, so its --eval --resume of a probe checkpoint drops
+    the head); a pos_embed of another grid size in --finetune is left out, the model keeps its own sin-cos table of the right size;
+  * mixup, layer decay, drop-path, F1 / mIoU, W&B / TensorBoard and multi-GPU probing are out of scope (WORLD_SIZE > 1 raises).
+
+    python main_linprobe.py --model vit_base_patch16 --finetune out/checkpoint-199.pth --transform_checkpoint_keys \\
+        --dataset_type synthetic --batch_size 128 --epochs 1
+"""
+import argparse
+import datetime
+import json
+import math
+import os
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+import models_vit
+import util.lr_sched as lr_sched
+import util.misc as misc
+from util.checkpoint_keys import to_vit_keys
+from util.lars import LARS
+
+
+def nullable_string(val):
+    return val if val else None
+
+
+def get_args_parser():
+    p = argparse.ArgumentParser("Cross-MAE Linear Probe", add_help=False)
+    p.add_argument("--batch_size", default=512, type=int, help="Batch size per GPU (effective batch size is batch_size * accum_iter * # gpus")
+    p.add_argument("--epochs", default=50, type=int)
+    p.add_argument("--accum_iter", type=int, default=1)
+    p.add_argument("--model", default="vit_base_patch16", type=str, metavar="MODEL")
+    p.add_argument("--input_size", default=224, type=int)
+    p.add_argument("--patch_size", default=16, type=int)
+    p.add_argument("--weight_decay", type=float, default=0.0, help="weight decay (default: 0 for linear probe following MoCo v1)")
+    p.add_argument("--lr", type=float, default=None, metavar="LR")
+    p.add_argument("--blr", type=float, default=0.1, metavar="LR", help="base learning rate: absolute_lr = base_lr * total_batch_size / 256")
+    p.add_argument("--min_lr", type=float, default=0.0, metavar="LR")
+    p.add_argument("--warmup_epochs", type=int, default=10, metavar="N")
+    p.add_argument("--finetune", default="", help="probe from this pre-training checkpoint")
+    p.add_argument("--global_pool", action="store_true")
+    p.set_defaults(global_pool=False)
+    p.add_argument("--cls_token", action="store_false", dest="global_pool", help="Use class token instead of global pool for classification")
+    p.add_argument("--transform_checkpoint_keys", action="store_true", default=False,
+                   help="map the pre-training model's keys to ViT keys (applied by itself when the checkpoint holds encoder_pos_embed)")
+    p.add_argument("--dataset_type", type=str, default="rgb", choices=["rgb", "sentinel", "euro_sat", "naip", "smart", "spacenetv1", "resisc45", "synthetic"])
+    p.add_argument("--nb_classes", default=62, type=int, help="number of the classification types")
+    p.add_argument("--output_dir", type=str, default=None)
+    p.add_argument("--output_dir_base", type=str, default="./out")
+    p.add_argument("--device", type=str, default="cuda:0")
+    p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--resume", type=nullable_string, default=None)
+    p.add_argument("--save_every", type=int, default=1)
+    p.add_argument("--start_epoch", default=0, type=int, metavar="N")
+    p.add_argument("--eval", action="store_true", help="Perform evaluation only")
+    # ---- additive flags of the MI355X build
+    p.add_argument("--synthetic_len", type=int, default=64, help="iterations per epoch of the synthetic loader (a quarter of it for evaluation)")
+    p.add_argument("--input_channels", type=int, default=3, help="bands of the synthetic loader / model")
+    p.add_argument("--print_freq", type=int, default=20, help="iterations between two drains of the device-side loss / accuracy counters")
+    p.add_argument("--embed_dim", type=int, default=None)
+    p.add_argument("--depth", type=int, default=None)
+    p.add_argument("--num_heads", type=int, default=None)
+    return p
+
+
+class SyntheticLoader:
+    """In-memory repeat loader: (samples [N, C, S, S] ~ N(0, 1), labels [N] int64) on `device`, the same batch every iteration."""
+
+    def __init__(self, batch, channels, size, classes, length, device, seed):
+        g = torch.Generator(device=device).manual_seed(seed)
+        self.samples = torch.randn(batch, channels, size, size, device=device, generator=g)
+        self.targets = torch.randint(0, classes, (batch,), device=device, generator=g)
+        self.length = length
+
+    def __len__(self):
+        return self.length
+
+    def __iter__(self):
+        for _ in range(self.length):
+            yield self.samples, self.targets
+
+
+def _autocast(device):
+    import contextlib
+    return torch.autocast("cuda", dtype=torch.bfloat16) if torch.device(device).type == "cuda" else contextlib.nullcontext()
+
+
+def train_one_epoch(model, data_loader, optimizer, device, epoch, args=None, log_writer=None):
+    """engine_finetune.py's epoch for the probe: LR schedule per iteration, loss / lr / acc1 / acc5 meters, gradient accumulation.  The
+    model computes the cross-entropy itself (`model(samples, targets)`); loss and hit counts are read every `print_freq` iterations."""
+    model.train(True)
+    metric_logger = misc.MetricLogger(delimiter="  ")
+    metric_logger.add_meter("lr", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
+    header = f"Epoch: [{epoch}]"
+    accum_iter, print_freq = args.accum_iter, getattr(args, "print_freq", 20)
+    optimizer.zero_grad(set_to_none=False)
+    n_iters = len(data_loader)
+    pending = []   # (device loss, lr)
+    gate = None
+    model.drain_counts()
+
+    def drain():
+        if not pending:
+            return
+        values = torch.stack([p[0].detach().float().reshape(()) for p in pending]).tolist()
+        top1, top5, seen = model.drain_counts()
+        for value, (_, lr) in zip(values, pending):
+            if not math.isfinite(value):
+                print(f"Loss is {value}, stopping training")
+                raise ValueError(f"Loss is {value}, stopping training")
+            metric_logger.update(loss=value)
+            metric_logger.update(lr=lr)
+        metric_logger.meters["acc1"].update(100.0 * top1 / seen, n=seen)
+        metric_logger.meters["acc5"].update(100.0 * top5 / seen, n=seen)
+        pending.clear()
+
+    for it, (samples, targets) in enumerate(metric_logger.log_every(data_loader, print_freq, header)):
+        if it % accum_iter == 0:
+            lr_sched.adjust_learning_rate(optimizer, it / n_iters + epoch, args)
+        samples, targets = samples.to(device, non_blocking=True), targets.to(device, non_blocking=True)
+        with _autocast(device):
+            loss, _ = model(samples, targets)
+        pending.append((loss, optimizer.param_groups[0]["lr"]))
+        gate = loss.detach().reshape(1) if it % accum_iter == 0 else gate + loss.detach().reshape(1)   # the update's losses, summed
+        (loss / accum_iter).backward()
+        if (it + 1) % accum_iter == 0:
+            optimizer.step(gate=gate)
+            optimizer.zero_grad(set_to_none=False)
+        if it % print_freq == 0 or it == n_iters - 1:
+            drain()   # exactly the iterations on which log_every prints the meters
+    drain()
+    metric_logger.synchronize_between_processes()
+    print("Averaged stats:", metric_logger)
+    return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
+
+
+@torch.no_grad()
+def evaluate(data_loader, model, device, args=None):
+    """-> {"loss", "acc1", "acc5"} over the loader, in eval mode (running statistics normalise); one host read at the end."""
+    model.eval()
+    model.drain_counts()
+    losses = []
+    for samples, targets in data_loader:
+        samples, targets = samples.to(device, non_blocking=True), targets.to(device, non_blocking=True)
+        with _autocast(device):
+            loss, _ = model(samples, targets)
+        losses.append(loss * samples.shape[0])
+    top1, top5, seen = model.drain_counts()
+    stats = {"loss": float(torch.stack(losses).sum()) / seen, "acc1": 100.0 * top1 / seen, "acc5": 100.0 * top5 / seen}
+    print("* Acc@1 {acc1:.3f} Acc@5 {acc5:.3f} loss {loss:.3f}".format(**stats))
+    return stats
+
+
+def load_pretrained(model, path, transform_keys=False):
+    """main_linprobe.py:441-512: load the trunk from a pre-training checkpoint; only the head (and fc_norm under global pooling) may be missing."""
+    checkpoint = torch.load(path, map_location="cpu", weights_only=False)
+    print("Load pre-trained checkpoint from: %s" % path)
+    sd = checkpoint["model"]
+    if transform_keys or "encoder_pos_embed" in sd:
+        sd = to_vit_keys(sd)
+    own = model.state_dict()
+    if "pos_embed" in sd and sd["pos_embed"].shape != own["pos_embed"].shape:
+        print(f"pos_embed {tuple(sd['pos_embed'].shape)} of the checkpoint does not fit {tuple(own['pos_embed'].shape)}: keeping the model's sin-cos table")
+        sd = {k: v for k, v in sd.items() if k != "pos_embed"}
+    msg = model.load_state_dict(sd, strict=False)
+    print(msg)
+    expected = {"head.weight", "head.bias"} | ({"fc_norm.weight", "fc_norm.bias"} if model.global_pool else set())
+    assert set(msg.missing_keys) == expected, sorted(set(msg.missing_keys) ^ expected)
+    return msg
+
+
+def main(args):
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("multi-GPU linear probing is not implemented: run main_linprobe.py as one process (the head is tiny; the "
+                                  "frozen trunk could be sharded over ranks, which this script does not do)")
+    print(f"job dir: {os.path.dirname(os.path.realpath(__file__))}")
+    print(f"{args}".replace(", ", ",\n"))
+    device = torch.device(args.device)
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    if args.dataset_type != "synthetic":
+        raise NotImplementedError(f"--dataset_type {args.dataset_type}: the reference's readers (util/datasets.py) depend on rasterio / fiona and are not "
+                                  "wired here; use --dataset_type synthetic or drive train_one_epoch / evaluate with your own iterable of (samples, labels)")
+    loader_train = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, args.synthetic_len, device, args.seed)
+    loader_val = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, max(1, args.synthetic_len // 4), device, args.seed)
+
+    geometry = {k: getattr(args, k) for k in ("embed_dim", "depth", "num_heads") if getattr(args, k) is not None}
+    model = models_vit.__dict__[args.model](patch_size=args.patch_size, img_size=args.input_size, in_chans=args.input_channels,
+                                            num_classes=args.nb_classes, drop_path_rate=0.0, global_pool=args.global_pool, **geometry)
+    if args.finetune and not args.eval:
+        load_pretrained(model, args.finetune, args.transform_checkpoint_keys)
+    model.probe_mode()
+    model.to(device)
+    print(f"Model = {model}")
+
+    batch_size_eff = args.batch_size * args.accum_iter
+    print("accumulate grad iterations: %d" % args.accum_iter)
+    print("effective batch size: %d" % batch_size_eff)
+    print("number of params (M): %.2f" % (sum(p.numel() for p in model.parameters() if p.requires_grad) / 1.0e6))
+    if args.lr is None:
+        args.lr = args.blr * batch_size_eff / 256
+    print("base lr: %.2e" % (args.lr * 256 / batch_size_eff))
+    print("actual lr: %.2e" % args.lr)
+    optimizer = LARS(model.head.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    print(optimizer)
+    misc.load_model(args=args, model_without_ddp=model, optimizer=optimizer, loss_scaler=None)
+
+    model_name = "_".join([args.model, f"i{args.input_size}-p{args.patch_size}", f"e{args.epochs}-we{args.warmup_epochs}",
+                           f"b{args.batch_size}-a{args.accum_iter}", f"lr{args.lr}", "_global_pool" if args.global_pool else "_cls_only", "linprobe"])
+    if args.output_dir is None:
+        args.output_dir = os.path.join(args.output_dir_base or ".", f"out_{model_name}")
+    print(f"Output directory: {args.output_dir}")
+    Path(args.output_dir).mkdir(parents=True, exist_ok=True)
+
+    if args.eval:
+        stats = evaluate(loader_val, model, device, args)
+        print(f"Evaluation on {len(loader_val) * args.batch_size} test images:\n\tacc1: {stats['acc1']:.2f}%\n\tacc5: {stats['acc5']:.2f}%")
+        return stats
+
+    print(f"Start training for {args.epochs} epochs")
+    start_time = time.time()
+    max_accuracy = 0.0
+    for epoch in range(args.start_epoch, args.epochs):
+        train_stats = train_one_epoch(model, loader_train, optimizer, device, epoch, args=args)
+        log_stats = {**{f"train_{k}": v for k, v in train_stats.items()}, "epoch": epoch}
+        if (epoch % args.save_every == 0 and epoch >= args.epochs / 2) or (epoch % 5 == 0 and epoch < args.epochs / 2) or epoch + 1 == args.epochs:
+            misc.save_model(args=args, model=model, model_without_ddp=model, optimizer=optimizer, loss_scaler=None, epoch=epoch)
+        test_stats = evaluate(loader_val, model, device, args)
+        max_accuracy = max(max_accuracy, test_stats["acc1"])
+        print(f"Max accuracy: {max_accuracy:.2f}%")
+        log_stats.update({f"test_{k}": v for k, v in test_stats.items()})
+        with open(os.path.join(args.output_dir, "log.jsonl"), mode="a", encoding="utf-8") as f:
+            f.write(json.dumps(log_stats) + "\n")
+    print(f"Training time {datetime.timedelta(seconds=int(time.time() - start_time))}")
+
+
+if __name__ == "__main__":
+    main(get_args_parser().parse_args())

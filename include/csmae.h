@@ -318,6 +318,32 @@ int csmae_cast_f32_to_bf16(long long n, const float* src, void* dst, void* strea
 int csmae_cast_bf16_to_f32(long long n, const void* src, float* dst, void* stream);
 int csmae_colsum(int dtype, long long M, int N, const void* x, long long ld, float* out, void* stream);
 
+/* ---- linear probing of the frozen encoder (main_linprobe.py:515-525; added within ABI version 7, csrc/linprobe.hip).  All fp32 except the
+ * token stream x of the pooling kernel. */
+/* models_vit.py:53-58 behind the last block: global_pool = 1: mean over tokens 1 .. T-1, then LayerNorm (fc_norm); 0: LayerNorm of token 0 (norm).
+ * x [N, T, D] fp32 or bf16 (16-byte aligned, D % 4 == 0, D <= 4096), feat [N, D] fp32.  global_pool with T = 1 is refused. */
+int csmae_probe_pool_fwd(int dtype, int global_pool, long long N, int T, int D, const void* x, const float* gamma, const float* beta, float eps,
+                         float* feat, void* stream);
+/* BatchNorm1d(D, affine=False) over the batch axis of feat [N, D].  training: biased batch variance normalises, running_mean / running_var move
+ * with `momentum` (unbiased variance), num_batches_tracked (nullable) += 1; N = 1 is refused.  Otherwise the running statistics normalise. */
+int csmae_bn1d_fwd(long long N, int D, const float* feat, float eps, float momentum, float* fbn, float* running_mean, float* running_var,
+                   long long* num_batches_tracked, int training, void* stream);
+/* logits [N, K] = x [N, D] w[K, D]^T + b (b nullable); any K, any D */
+int csmae_head_linear_fwd(long long N, int D, int K, const float* x, const float* w, const float* b, float* logits, void* stream);
+/* dw [K, D] (+)= gscale dlogits^T x, db [K] (+)= gscale sum_n dlogits (db nullable; gscale: nullable device scalar, 1 when absent) */
+int csmae_head_linear_bwd(long long N, int D, int K, const float* dlogits, const float* x, const float* gscale, float* dw, float* db, int accumulate,
+                          void* stream);
+/* mean cross-entropy of logits [N, K] against labels [N] (int64) -> loss[0]; dlogits (nullable) = gout (softmax - onehot) / N (gout: nullable
+ * device scalar); counts (nullable) [2] (+)= rows whose label is in the top 1 / top min(5, K) (fewer than k logits strictly greater than the
+ * label's).  A label outside [0, K) gives a NaN loss and gradient row and no hit.  scratch: 3 N floats. */
+int csmae_softmax_ce(long long N, int K, const float* logits, const long long* labels, const float* gout, float* scratch, float* loss, float* dlogits,
+                     float* counts, int accumulate_counts, void* stream);
+/* LARS (util/lars.py:27-57) over ntensors tensors: table (device int64 [ntensors][5]) = {p, g, mu addresses, numel, ndim > 1}.  Matrices:
+ * dp = q (g + wd p), q = trust |p| / |dp| (1 when either norm is 0); vectors: dp = g.  mu = momentum mu + dp, p -= lr mu.  norms: ntensors x 128
+ * floats of scratch.  gate: nullable device scalar, a non-finite value skips the whole update.  Two launches, no host synchronisation. */
+int csmae_lars_step(int ntensors, const long long* table, float lr, float weight_decay, float momentum, float trust, float* norms, const float* gate,
+                    void* stream);
+
 
 /* ---- a stream confined to a subset of the compute units (ABI version 5).  The reference overlaps DDP's bucket all-reduces and autograd's
  * weight-gradient work with the main chain on CUDA streams that share every SM (main_pretrain.py:417-421); on MI355X a GEMM workgroup owns a
