@@ -22,7 +22,8 @@ LOSS_KINDS = {"mse": 0, "l2": 1, "mae": 2, "l1": 3, "bce": 4, "none": 5}
 SSIM_KINDS = {"ssim": ("none", 1, 1.0), "ms_ssim": ("none", 5, 1.0), "mse_ssim": ("mse", 1, 0.1), "mse_ms_ssim": ("mse", 5, 0.1)}
 
 _ADDED_WITHIN_ABI = ("csmae_attn_route", "csmae_attn_stream_mode", "csmae_probe_pool_fwd", "csmae_bn1d_fwd", "csmae_head_linear_fwd",
-                     "csmae_head_linear_bwd", "csmae_softmax_ce", "csmae_lars_step")   # additions that left ABI_VERSION alone (see load())
+                     "csmae_head_linear_bwd", "csmae_softmax_ce", "csmae_lars_step", "csmae_probe_pool_bwd", "csmae_head_linear_dx", "csmae_soft_ce",
+                     "csmae_mixup_target", "csmae_mixup_cutmix", "csmae_pos_embed_grad")   # additions that left ABI_VERSION alone (see load())
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSMAE_LIB_PATH") or os.path.join(_HERE, "libcsmae_hip.so")   # (override: A/B builds of tools/)
 
@@ -100,6 +101,12 @@ _SIGNATURES = {
     "csmae_head_linear_bwd": [L, I, I, P, P, P, P, P, I, P],
     "csmae_softmax_ce": [L, I, P, P, P, P, P, P, P, I, P],
     "csmae_lars_step": [I, P, F, F, F, F, P, P, P],
+    "csmae_probe_pool_bwd": [I, I, L, I, I, P, P, P, F, P, P, P, P, I, P],
+    "csmae_head_linear_dx": [L, I, I, P, P, P, P, P],
+    "csmae_soft_ce": [L, I, P, P, P, P, P, P, P],
+    "csmae_mixup_target": [L, I, P, F, F, P, P],
+    "csmae_mixup_cutmix": [I, L, I, I, I, P, P, F, I, I, I, I, P],
+    "csmae_pos_embed_grad": [I, L, I, I, P, P, I, P],
     "csmae_stream_create_cu_mask": [I, P, P],
     "csmae_stream_destroy": [P],
 }

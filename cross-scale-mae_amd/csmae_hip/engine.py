@@ -29,6 +29,11 @@ from . import BF16, EPI_ATOMIC, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_RESID, F32, S
 from . import trace
 
 _FROZEN = ("encoder_pos_embed", "decoder_pos_embed")
+_GEN_GONE = ("csmae_hip: backward of a forward whose activations are gone — the model ran another forward (training, eval "
+             "or viz) in between; the engine keeps ONE activation workspace, so call loss.backward() before the next "
+             "model(...) (accumulate gradients across backward calls, not across forwards)")
+_GEN_TWICE = ("csmae_hip: backward called twice for the same forward (retain_graph is not supported: the reverse pass "
+              "consumes the workspace)")
 
 
 def _round_up(x, m):
@@ -1097,21 +1102,28 @@ class Engine:
             lat = ws.lat32
         return lat.view(imgs.shape[0], ws.Te, c["D"]).clone(), ws.mask.clone(), ws.ids_restore.clone()
 
-    def encode_stream(self, imgs: torch.Tensor, mask_ratio: float, noise: torch.Tensor):
+    def encode_stream(self, imgs: torch.Tensor, mask_ratio: float, noise: torch.Tensor, training: bool = False):
         """The encoder half of `encode`, leaving its result where the blocks wrote it: the workspace whose `enc["x"][Ne]` [N * (keep+1), D] is
-        the residual stream behind the last block (fp32, or bf16 in throughput mode) — valid until the engine's next pass."""
+        the residual stream behind the last block (fp32, or bf16 in throughput mode) — valid until the engine's next pass.  `training`: the
+        activations are kept for ONE backward_stream() call (the forward's generation is `self.gen`)."""
         assert self.views == 1, "encode()/decode() run on a single-view (Baseline-variant) engine"
         c = self.cfg
         N = imgs.shape[0]
         keep = int(c["L"] * (1 - mask_ratio))
         if keep < 1:
             raise ValueError(f"mask_ratio={mask_ratio} keeps no patch (L={c['L']})")
+        if training and self.fp8:
+            raise NotImplementedError("encode_stream(training=True): the stand-alone encoder's backward is not implemented for fp8 engines")
         if self.ws is None or self.ws.N != N or self.ws.keep != keep:
             self.ws = None
+            self._dw_cache.clear()
             self.ws = Workspace(self, N, keep)
         ws, P = self.ws, self.flat.P
         self.st = st = ops.stream()
         L, D = c["L"], c["D"]
+        self.gen += 1   # (whatever an earlier forward left in the workspace is gone)
+        if training:
+            self._saved = dict(stream=True, N=N, keep=keep, gen=self.gen)
         self._opt_gate()
         self._refresh_lp()
         self._ks_wait()
@@ -1124,6 +1136,69 @@ class Engine:
         for i in range(c["Ne"]):
             self._block_fwd(ws.enc, i, f"encoder.{i}.", ws.Me, D, c["He"], N, ws.Te)
         return ws
+
+    def stream_grad(self):
+        """Where backward_stream reads the gradient of the residual stream behind the last block: [N * (keep+1), D] in the stream's dtype.  A producer
+        that writes it here (every element) saves backward_stream a copy."""
+        return self.ws.dres_e if self.res_dtype == torch.float32 else self.ws.dres_e_lp[0]
+
+    def stream_backward_ready(self, gen: Optional[int] = None):
+        """Raises unless the workspace still holds the activations of the encode_stream(training=True) call of generation `gen` (None: the last
+        one) and their backward has not run yet."""
+        sv = self._saved
+        if sv is None or not sv.get("stream"):
+            if gen is not None and gen != self.gen:
+                raise RuntimeError(_GEN_GONE)
+            raise RuntimeError("backward_stream() called without a preceding encode_stream(training=True)")
+        if (gen is not None and gen != sv["gen"]) or sv["gen"] != self.gen:
+            raise RuntimeError(_GEN_GONE)
+        if sv["gen"] == self._gen_done:
+            raise RuntimeError(_GEN_TWICE)
+
+    def backward_stream(self, dres: torch.Tensor, accumulate: bool, gen: Optional[int] = None, loss: Optional[torch.Tensor] = None):
+        """Reverse pass of the last encode_stream(..., training=True) of a single-view engine, from `dres`, the gradient of the residual stream behind
+        the last block ([N, keep+1, D], the stream's dtype): block backward, LayerNorm parameter gradients, cls token, patch embedding, and the
+        position-embedding gradient — the token order must be the identity (mask ratio 0 with an increasing noise ramp), so that row t of every
+        sample took pos_embed[t].  Gradients land in the flat buffer (`accumulate`: on top of what it holds; otherwise it is cleared first) and
+        are handed to the `.grad` slots.  `loss`: device scalar behind these gradients, for FusedAdamW's update gate."""
+        if self.fp8:
+            raise NotImplementedError("backward_stream: the stand-alone encoder's backward is not implemented for fp8 engines")
+        if getattr(self.module, "_dp", None) is not None:
+            raise NotImplementedError("backward_stream: data-parallel gradient hooks are not implemented for the stand-alone encoder's backward")
+        assert self.views == 1
+        self.stream_backward_ready(gen)
+        c, ws, sv = self.cfg, self.ws, self._saved
+        N, keep, D = sv["N"], sv["keep"], c["D"]
+        if keep != c["L"]:
+            raise ValueError("backward_stream: the position-embedding gradient needs every patch in its place (mask_ratio 0)")
+        self._gen_done = sv["gen"]
+        self.st = st = ops.stream()
+        self._opt_gate()   # (the gradient buffer and the gate slot are the optimizer step's inputs)
+        self.main = torch.cuda.current_stream()
+        if self.side is None:
+            self.side = self._new_side()
+        self._ev_i, self._tog = 0, 0
+        self._side_reads.clear()
+        with trace.range_("csmae.backward.encoder"):
+            if not accumulate:
+                self.flat.g[: self.flat.total].zero_()
+            if loss is not None:
+                ops.gate_accumulate(loss, self.flat.gate, accumulate, st=st)
+            buf = self.stream_grad()
+            if dres.dtype != buf.dtype or dres.numel() != buf.numel():
+                raise ValueError(f"backward_stream: dres must be {tuple(buf.shape)} elements of {buf.dtype}, got {tuple(dres.shape)} of {dres.dtype}")
+            if dres.data_ptr() != buf.data_ptr():
+                buf.copy_(dres.reshape(buf.shape))
+            if self.res_dtype == torch.float32:   # the blocks' GEMMs read the low-precision twin of the fp32 stream gradient
+                ops.latent_grad_finish(ws.dres_e, None, 1.0, ws.dres_e_lp[0], ws.B2, ws.Te, st=st)
+            first = self._encoder_bwd()
+            if self.flat.params["encoder_pos_embed"].requires_grad:   # (the slot _FROZEN keeps closed in pre-training)
+                ops.pos_embed_grad(first.view(N, ws.Te, D), self.flat.G("encoder_pos_embed").view(ws.Te, D), accumulate=True, st=st)
+        for name, p in self.flat.params.items():
+            if p.requires_grad:
+                p.grad = self.flat.grad_views[name]
+            elif not name.startswith("decoder"):   # a parameter the user froze: its slot is cleared, as in _backward
+                self.flat.grad_views[name].zero_()
 
     def decode(self, latent: torch.Tensor, ids_restore: torch.Tensor):
         """`forward_decoder` (MAE_ViT_Baseline.py:268-297): decoder_embed, mask-token fill + unshuffle + pos-embed, decoder blocks,
@@ -1179,6 +1254,31 @@ class Engine:
             self._backward(gout, accumulate, gen)
         outer.wait_stream(inner)
 
+    def _encoder_bwd(self, dp=None):
+        """The trunk's reverse pass, shared by the training step and backward_stream: the encoder blocks from the residual-stream gradient in
+        ws.dres_e_lp[0] (and ws.dres_e with an fp32 stream), their LayerNorm parameter gradients, the cls-token gradient and the patch-embed
+        weight gradient.  Returns the buffer that holds the stream gradient in front of the first block ([B2 * Te, D], the stream's dtype)."""
+        c, ws, st, G = self.cfg, self.ws, self.st, self.flat.G
+        B2, Te, D, keep = ws.B2, ws.Te, c["D"], self._saved["keep"]
+        lp_stream = self.res_dtype != torch.float32
+        self._fp8_cur = None
+        pe, flushed = ws.ln_part_e, c["Ne"]
+        fe = lp_stream and self._ln_fused_bwd(ws.Me, D)
+        ke_ = 0
+        for i in reversed(range(c["Ne"])):
+            ke_ = self._block_bwd(ws.enc, i, f"encoder.{i}.", ws.Me, D, c["He"], B2, Te, None if lp_stream else ws.dres_e, ws.dres_e_lp, ke_, (pe[2 * i], pe[2 * i + 1]),
+                                  lps8=ws.dres_e_8 if (self.fp8 and self.fp8_dw and lp_stream) else None)
+            if dp is not None and dp.wants(("enc", i)):
+                self._ln_flush(pe, self._goff_e, 2 * i, 2 * flushed, ws.Me, D, fused=fe)   # the bucket's LayerNorm gradients must be final before its exchange
+                flushed = i
+                dp.grads_ready(self.flat, ("enc", i), also=self.side if not (ops._timer is not None or os.environ.get("CSMAE_DW_MAIN")) else None)
+        self._ln_flush(pe, self._goff_e, 0, 2 * flushed, ws.Me, D, fused=fe)
+        first = ws.dres_e_lp[ke_] if lp_stream else ws.dres_e
+        ops.embed_assemble_bwd(first, ws.dtok_lp, G("cls_token").view(D), B2, keep, st=st)
+        self._join_side()
+        ops.DwGroup([(ws.dtok_lp, ws.a_pe[:, : c["P"]], G("patch_embed.proj.weight").view(D, c["P"]), G("patch_embed.proj.bias"))], ws.dw_ws).launch(256, st=st)
+        return first
+
     def _backward(self, gout: torch.Tensor, accumulate: bool, gen: Optional[int] = None):
         """Reverse pass of the LAST forward (the activations live in the engine's one workspace).  `gen` = the forward this call
         belongs to (the autograd node passes it): a forward that has been overwritten by a later one, or whose backward already ran,
@@ -1186,13 +1286,12 @@ class Engine:
         c, ws, sv = self.cfg, self.ws, self._saved
         if sv is None:
             raise RuntimeError("backward() called without a preceding forward()")
+        if sv.get("stream"):
+            raise RuntimeError("backward() after encode_stream(): the stand-alone encoder's reverse pass is backward_stream()")
         if gen is not None and gen != sv["gen"]:
-            raise RuntimeError("csmae_hip: backward of a forward whose activations are gone — the model ran another forward (training, eval "
-                               "or viz) in between; the engine keeps ONE activation workspace, so call loss.backward() before the next "
-                               "model(...) (accumulate gradients across backward calls, not across forwards)")
+            raise RuntimeError(_GEN_GONE)
         if sv["gen"] == self._gen_done:
-            raise RuntimeError("csmae_hip: backward called twice for the same forward (retain_graph is not supported: the reverse pass "
-                               "consumes the workspace)")
+            raise RuntimeError(_GEN_TWICE)
         self._gen_done = sv["gen"]
         P, G = self.flat.P, self.flat.G
         self.st = st = ops.stream()
@@ -1326,21 +1425,7 @@ class Engine:
             ops.ntxent_bwd(ws.zc, ws.inv_norm, ws.E, ws.neg, ws.gout, ws.dpool, N, st=st)
             dpool = ws.dpool
         ops.latent_grad_finish(ws.dres_e, dpool, 1.0 / keep, ws.dres_e_lp[0], B2, Te, st=st)
-        self._fp8_cur = None
-        pe, flushed = ws.ln_part_e, c["Ne"]
-        fe = lp_stream and self._ln_fused_bwd(ws.Me, D)
-        ke_ = 0
-        for i in reversed(range(c["Ne"])):
-            ke_ = self._block_bwd(ws.enc, i, f"encoder.{i}.", ws.Me, D, c["He"], B2, Te, None if lp_stream else ws.dres_e, ws.dres_e_lp, ke_, (pe[2 * i], pe[2 * i + 1]),
-                                  lps8=ws.dres_e_8 if (self.fp8 and self.fp8_dw and lp_stream) else None)
-            if dp is not None and dp.wants(("enc", i)):
-                self._ln_flush(pe, self._goff_e, 2 * i, 2 * flushed, ws.Me, D, fused=fe)   # the bucket's LayerNorm gradients must be final before its exchange
-                flushed = i
-                dp.grads_ready(self.flat, ("enc", i), also=self.side if not (ops._timer is not None or os.environ.get("CSMAE_DW_MAIN")) else None)
-        self._ln_flush(pe, self._goff_e, 0, 2 * flushed, ws.Me, D, fused=fe)
-        ops.embed_assemble_bwd(ws.dres_e_lp[ke_] if lp_stream else ws.dres_e, ws.dtok_lp, G("cls_token").view(D), B2, keep, st=st)
-        self._join_side()
-        ops.DwGroup([(ws.dtok_lp, ws.a_pe[:, : c["P"]], G("patch_embed.proj.weight").view(D, c["P"]), G("patch_embed.proj.bias"))], ws.dw_ws).launch(256, st=st)
+        self._encoder_bwd(dp)
         if dp is not None:
             dp.grads_ready(self.flat, "stem")
             dp.backward_done(self.flat)

@@ -698,4 +698,71 @@ def lars_step(table, norms, lr, weight_decay, momentum, trust_coefficient, gate=
                                  st if st is not None else stream()), "csmae_lars_step")
 
 
+# ---- end-to-end fine-tuning (csrc/finetune.hip)
+def probe_pool_bwd(x, dfeat, gamma, dres, dgamma, dbeta, global_pool, eps=1e-6, accumulate=False, partial=None, st=None):
+    """Reverse of probe_pool_fwd: dres [N, T, D] (the dtype of x, every element written) from dfeat [N, D]; dgamma / dbeta [D] (+)= over the batch."""
+    N, T, D = x.shape
+    if global_pool and T < 2:   # (the forward's refusal, before anything is launched)
+        raise ValueError(f"global_pool averages tokens 1 .. T-1: T = {T} leaves nothing to average")
+    assert x.is_contiguous() and dres.is_contiguous() and dres.shape == x.shape and dres.dtype == x.dtype and dfeat.shape == (N, D)
+    assert gamma.numel() == D and dgamma.numel() == D and dbeta.numel() == D
+    _f32c(dfeat, gamma, dgamma, dbeta, partial)
+    if partial is None:
+        partial = torch.empty(2 * N * D, device=x.device, dtype=torch.float32)
+    assert partial.numel() >= 2 * N * D
+    check(load().csmae_probe_pool_bwd(dt(x), int(bool(global_pool)), N, T, D, _p(x), _p(dfeat), _p(gamma), float(eps), _p(dres), _p(partial), _p(dgamma),
+                                      _p(dbeta), int(bool(accumulate)), st if st is not None else stream()), "csmae_probe_pool_bwd")
+    return dres
+
+
+def head_linear_dx(dlogits, w, dx, gscale=None, st=None):
+    """dx [N, D] = gscale dlogits [N, K] w [K, D] (gscale: device scalar or None)."""
+    (N, K), D = dlogits.shape, w.shape[1]
+    assert w.shape == (K, D) and dx.shape == (N, D)
+    _f32c(dlogits, w, dx, gscale)
+    check(load().csmae_head_linear_dx(N, D, K, _p(dlogits), _p(w), _p(gscale), _p(dx), st if st is not None else stream()), "csmae_head_linear_dx")
+    return dx
+
+
+def soft_ce(logits, target, loss, dlogits=None, gout=None, scratch=None, st=None):
+    """loss[0] = mean soft-target cross-entropy against dense targets [N, K]; dlogits = gout (softmax sum(target) - target) / N."""
+    N, K = logits.shape
+    assert target.shape == (N, K) and (dlogits is None or dlogits.shape == logits.shape)
+    _f32c(logits, target, loss, dlogits, gout)
+    if scratch is None:
+        scratch = torch.empty(N, device=logits.device, dtype=torch.float32)
+    assert scratch.numel() >= N
+    check(load().csmae_soft_ce(N, K, _p(logits), _p(target), _p(gout), _p(scratch), _p(loss), _p(dlogits), st if st is not None else stream()), "csmae_soft_ce")
+
+
+def mixup_target(labels, target, lam=1.0, smoothing=0.0, st=None):
+    """target [N, K] = lam onehot(y) + (1 - lam) onehot(y flipped), label-smoothed (timm mixup_target); lam = 1: plain label smoothing."""
+    N, K = target.shape
+    assert labels.dtype == torch.int64 and labels.numel() == N and labels.is_contiguous()
+    _f32c(target)
+    check(load().csmae_mixup_target(N, K, _p(labels), float(lam), float(smoothing), _p(target), st if st is not None else stream()), "csmae_mixup_target")
+    return target
+
+
+def mixup_cutmix(x, out, lam=1.0, box=None, st=None):
+    """out[n] = lam x[n] + (1 - lam) x[N-1-n] (box None), or x[n] with box = (yl, yh, xl, xh) copied from x[N-1-n].  Out of place, N even."""
+    N, C, H, W = x.shape
+    if N % 2:   # (timm's assertion, before anything is launched)
+        raise ValueError(f"Batch size should be even when using this (got {N})")
+    assert out.shape == x.shape and out.data_ptr() != x.data_ptr()
+    _f32c(x, out)
+    yl, yh, xl, xh = (0, 0, 0, 0) if box is None else (int(v) for v in box)
+    check(load().csmae_mixup_cutmix(int(box is not None), N, C, H, W, _p(x), _p(out), float(lam), yl, yh, xl, xh, st if st is not None else stream()),
+          "csmae_mixup_cutmix")
+    return out
+
+
+def pos_embed_grad(dres, dpos, accumulate=False, st=None):
+    """dpos [T, D] fp32 (+)= sum over the batch of dres [N, T, D] (fp32 or bf16)."""
+    N, T, D = dres.shape
+    assert dres.is_contiguous() and dpos.numel() == T * D
+    _f32c(dpos)
+    check(load().csmae_pos_embed_grad(dt(dres), N, T, D, _p(dres), _p(dpos), int(bool(accumulate)), st if st is not None else stream()), "csmae_pos_embed_grad")
+
+
 __all__ = [n for n in dir() if not n.startswith("_")]

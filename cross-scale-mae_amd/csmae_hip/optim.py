@@ -45,7 +45,9 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _bind(self):
         from .engine import FlatParams
-        first = self.param_groups[0]["params"][0] if self.param_groups[0]["params"] else self.param_groups[1]["params"][0]
+        first = next((g["params"][0] for g in self.param_groups if g["params"]), None)   # (any number of groups: layer-wise decay makes 2 (depth + 2))
+        if first is None:
+            raise RuntimeError("FusedAdamW: no parameters to step")
         flat = FlatParams.owner_of(first)
         if flat is None:
             raise RuntimeError("FusedAdamW: parameters are not homed in a csmae_hip flat buffer yet — run one forward pass of the model on the "

@@ -1,4 +1,4 @@
-"""Plain ViT encoder + classification head for linear probing (reference models_vit.py: timm's VisionTransformer with optional global
+"""Plain ViT encoder + classification head for linear probing and fine-tuning (reference models_vit.py: timm's VisionTransformer with optional global
 average pooling): the reference's factories, keywords and parameter names, so that `util.checkpoint_keys.to_vit_keys(checkpoint["model"])`
 loads with strict=False leaving only `head.*` (and `fc_norm.*` under global pooling) missing.  Every FLOP runs on the MI355X:
 
@@ -6,8 +6,10 @@ loads with strict=False leaving only `head.*` (and `fc_norm.*` under global pool
   token order is the identity): the resident / streaming attention kernels, bf16 MFMA under autocast, exact fp32 otherwise;
 * pooling + final norm, the probe's BatchNorm1d, the classifier, cross-entropy with top-1 / top-5 counts run in csrc/linprobe.hip.
 
-Only the head is trainable (probe mode, main_linprobe.py:515-525): `loss.backward()` fills `head.1.weight.grad` / `head.1.bias.grad`
-through one coarse autograd node.  Fine-tuning the trunk is not implemented and raises."""
+Probe mode (main_linprobe.py:515-525) trains only the head: `loss.backward()` fills `head.1.weight.grad` / `head.1.bias.grad` through one
+coarse autograd node.  Fine-tune mode (`finetune_mode()`, main_finetune.py) trains everything: head, final norm and trunk share one flat
+buffer, and `loss.backward()` runs the head's backward of csrc/finetune.hip and `Engine.backward_stream`.  A model in neither mode refuses
+trunk gradients; dropout / drop-path > 0 is not implemented and raises."""
 from functools import partial
 
 import torch
@@ -22,8 +24,10 @@ class _TrunkView:
     """The trunk's Parameters under the pre-training names the engine reads (encoder.<i>.*, encoder_pos_embed, ...), plus the few
     decoder-side slots its constructor looks up (never computed with: the stand-alone encoder half is all that runs)."""
 
-    def __init__(self, vit, P):
-        named = from_vit_keys(dict(vit.named_parameters()))
+    def __init__(self, vit, P, extra=()):
+        own = dict(vit.named_parameters())
+        named = from_vit_keys(own)
+        named.update((n, own[n]) for n in extra if n in own)   # fine-tune mode: head.* and fc_norm.* live in the same flat buffer, under their own names
         dev = vit.cls_token.device
         stub = lambda *shape: nn.Parameter(torch.zeros(*shape, device=dev), requires_grad=False)
         named.update({"decoder_norm.weight": stub(_STUB_DD), "decoder_norm.bias": stub(_STUB_DD), "decoder_pred.weight": stub(P, _STUB_DD)})
@@ -59,6 +63,26 @@ class _ProbeFn(torch.autograd.Function):
                     p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
             ops.head_linear_bwd(ctx.dlogits, ctx.fbn, lin.weight.grad, None if lin.bias is None else lin.bias.grad, accumulate=had,
                                 gscale=gloss.detach().reshape(1).to(torch.float32).contiguous())
+        return (None,) * 4
+
+
+class _FinetuneFn(torch.autograd.Function):
+    """One autograd node for trunk + head + loss in fine-tune mode.  backward = classifier dW / db and dX, pooling + final-norm backward into the
+    residual-stream gradient, then the trunk's reverse pass (Engine.backward_stream); every gradient lands in the flat buffer, whose views
+    become the `.grad`s.  A backward into existing gradients accumulates."""
+
+    @staticmethod
+    def forward(ctx, model, x, target, anchor):
+        loss, logits, eng, feat, dlogits = model._finetune_pass(x, target, want_grad=True)
+        ctx.model, ctx.eng, ctx.gen, ctx.feat, ctx.dlogits, ctx.loss = model, eng, eng.gen, feat, dlogits, loss.detach()   # (not the output itself: no cycle through its grad_fn)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(logits)
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, gloss, glogits):
+        if gloss is not None:
+            ctx.model._finetune_backward(ctx.eng, ctx.gen, ctx.feat, ctx.dlogits, ctx.loss, gloss.detach().reshape(1).to(torch.float32).contiguous())
         return (None,) * 4
 
 
@@ -98,6 +122,8 @@ class VisionTransformer(nn.Module):
         table = get_2d_sincos_pos_embed(embed_dim, int(num_patches ** 0.5), cls_token=True)
         self.pos_embed.data.copy_(torch.from_numpy(table).float().unsqueeze(0))
         self.compute_dtype = None  # None: bf16 MFMA under torch autocast, exact fp32 otherwise; or force torch.bfloat16 / torch.float32
+        self.smoothing = 0.0       # fine-tune mode, training: label smoothing applied to integer labels (main_finetune.py sets it)
+        self._finetune = False
         self._flat, self._view, self._engines, self._bufs = None, None, {}, {}
 
     @staticmethod
@@ -124,6 +150,21 @@ class VisionTransformer(nn.Module):
             p.requires_grad = True
         return self
 
+    # ---- fine-tune mode (main_finetune.py)
+    def finetune_mode(self):
+        """Everything trains: `forward(x, target)` returns a loss that is differentiable w.r.t. every parameter.  head.* and the final norm move
+        into the trunk's flat buffer at the next forward (one buffer for FusedAdamW, `.grad`s are views of its gradient twin)."""
+        if isinstance(self.head, nn.Sequential):
+            raise RuntimeError("finetune_mode() on a model in probe mode: the probe head (BatchNorm1d + Linear) is not the fine-tune head")
+        for p in self.parameters():
+            p.requires_grad = True
+        self._finetune = True
+        self._flat, self._engines = None, {}   # (re-homed with the head at the next forward)
+        return self
+
+    def no_weight_decay(self):
+        return {"pos_embed", "cls_token"}
+
     def _linear(self):
         return self.head[1] if isinstance(self.head, nn.Sequential) else self.head
 
@@ -142,7 +183,8 @@ class VisionTransformer(nn.Module):
         if not self.cls_token.is_cuda:
             raise RuntimeError("model parameters are on the CPU: call model.to('cuda') first")
         if self._flat is None or not self._flat.still_homed():
-            self._view = _TrunkView(self, self._cfg()["P"])
+            extra = [n for n, _ in self.named_parameters() if n.startswith(("head.", "fc_norm."))] if self._finetune else ()
+            self._view = _TrunkView(self, self._cfg()["P"], extra)
             self._flat = FlatParams(self._view, self.cls_token.device)
             self._engines = {}
         dtype = self.compute_dtype
@@ -165,8 +207,9 @@ class VisionTransformer(nn.Module):
             raise AssertionError(f"input {tuple(x.shape)} does not match (N, {self.in_chans}, {self.img_size}, {self.img_size})")
         return x.contiguous().float()
 
-    def _features(self, x):
-        """feat [N, D] fp32 in a buffer of the model's (overwritten by the next call)."""
+    def _features(self, x, training=False):
+        """feat [N, D] fp32 in a buffer of the model's (overwritten by the next call).  `training`: the trunk keeps its activations for one
+        Engine.backward_stream."""
         from csmae_hip import ops
         x = self._check_input(x)
         eng = self._engine(x)
@@ -174,7 +217,7 @@ class VisionTransformer(nn.Module):
         ramp = self._bufs.get("ramp")
         if ramp is None or ramp.shape != (N, L) or ramp.device != x.device:   # increasing noise: random_masking's argsort is the identity, nothing is dropped
             ramp = self._bufs["ramp"] = (torch.arange(L, dtype=torch.float32, device=x.device) / L).expand(N, L).contiguous()
-        ws = eng.encode_stream(x, 0.0, ramp)
+        ws = eng.encode_stream(x, 0.0, ramp, training=training)
         tokens = ws.enc["x"][len(self.blocks)].view(N, L + 1, D)   # the residual stream behind the last block: fp32, or bf16 in throughput mode
         norm = self.fc_norm if self.global_pool else self.norm
         feat = self._buf("feat", (N, D))
@@ -206,6 +249,55 @@ class VisionTransformer(nn.Module):
         self._seen += N
         return loss.reshape(()), logits, fbn, dlogits
 
+    def _finetune_pass(self, x, target, want_grad):
+        """Fine-tune mode: trunk, pooling + final norm, classifier, criterion.  `target`: int64 labels [N] (cross-entropy with the top-1 / top-5
+        counters; label-smoothed by `self.smoothing` while training) or dense float targets [N, K] (soft-target cross-entropy).
+        -> loss, logits, engine, feat, dlogits (for a unit upstream gradient; None unless want_grad)."""
+        from csmae_hip import ops
+        feat = self._features(x, training=want_grad)
+        eng = self._engine(x)
+        N, K, dev = feat.shape[0], self.num_classes, feat.device
+        logits = torch.empty(N, K, device=dev, dtype=torch.float32)
+        ops.head_linear_fwd(feat, self.head.weight.detach(), None if self.head.bias is None else self.head.bias.detach(), logits)
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        dlogits = torch.empty(N, K, device=dev, dtype=torch.float32) if want_grad else None
+        if target.device != dev:
+            raise ValueError("target must live on the model's device")
+        if target.dtype == torch.int64 and target.shape == (N,):
+            smoothing = float(self.smoothing) if self.training else 0.0
+            if smoothing > 0.0:   # LabelSmoothingCrossEntropy(s) = soft-target cross-entropy on the smoothed one-hot rows
+                dense = ops.mixup_target(target.contiguous(), self._buf("dense_target", (N, K)), lam=1.0, smoothing=smoothing)
+                ops.soft_ce(logits, dense, loss, dlogits=dlogits, scratch=self._buf("ce_scratch", (3 * N,)))
+            else:
+                ops.softmax_ce(logits, target.contiguous(), loss, dlogits=dlogits, counts=self.hit_counts(), accumulate_counts=True,
+                               scratch=self._buf("ce_scratch", (3 * N,)))
+                self._seen += N
+        elif target.is_floating_point() and target.shape == (N, K):
+            ops.soft_ce(logits, target.float().contiguous(), loss, dlogits=dlogits, scratch=self._buf("ce_scratch", (3 * N,)))
+        else:
+            raise ValueError(f"target must be int64 labels of shape ({N},) or dense float targets of shape ({N}, {K})")
+        return loss.reshape(()), logits, eng, feat, dlogits
+
+    def _finetune_backward(self, eng, gen, feat, dlogits, loss, gscale):
+        from csmae_hip import ops
+        eng.stream_backward_ready(gen)   # (before anything is written: feat and the workspace must still be this forward's)
+        flat = self._flat
+        G = flat.G
+        N, T, D = feat.shape[0], self.patch_embed.num_patches + 1, self.embed_dim
+        accumulate = any(p.grad is not None for p in flat.params.values())
+        if not accumulate:
+            flat.g[: flat.total].zero_()
+        ops.gate_accumulate(loss.reshape(1), flat.gate, accumulate)   # FusedAdamW skips the update on the device when a loss behind it was not finite
+        ops.head_linear_bwd(dlogits, feat, G("head.weight"), None if self.head.bias is None else G("head.bias"), accumulate=True, gscale=gscale)
+        dfeat = self._buf("dfeat", (N, D))
+        ops.head_linear_dx(dlogits, self.head.weight.detach(), dfeat, gscale=gscale)
+        norm, name = (self.fc_norm, "fc_norm") if self.global_pool else (self.norm, "encoder_norm")
+        tokens = eng.ws.enc["x"][len(self.blocks)].view(N, T, D)
+        dres = eng.stream_grad().view(N, T, D)
+        ops.probe_pool_bwd(tokens, dfeat, norm.weight.detach(), dres, G(name + ".weight"), G(name + ".bias"), self.global_pool, eps=norm.eps,
+                           accumulate=True, partial=self._buf("pool_partial", (2 * N * D,)))
+        eng.backward_stream(dres, accumulate=True, gen=gen)   # (on top of the head's gradients: the buffer was cleared above)
+
     # ---- accuracy counters: top-1 / top-5 hits of every `forward(x, target)` since the last drain, kept on the device
     def hit_counts(self):
         c = self.__dict__.get("_counts")
@@ -229,15 +321,24 @@ class VisionTransformer(nn.Module):
         return self._features(x).clone()
 
     def forward(self, x, target=None):
-        """logits [N, K]; with `target` (int64 class indices): (mean cross-entropy loss, logits), the loss differentiable w.r.t. the head."""
+        """logits [N, K]; with `target`: (loss, logits).  Probe mode: int64 class indices, mean cross-entropy, differentiable w.r.t. the head.
+        Fine-tune mode: int64 class indices or dense float targets [N, K] (mixup), differentiable w.r.t. every parameter."""
         trainable = [n for n, p in self.named_parameters() if p.requires_grad]
-        if target is not None and torch.is_grad_enabled() and trainable:
-            if any(not n.startswith("head.") for n in trainable):
-                raise NotImplementedError("only the head is trainable on the MI355X path (linear probing): freeze the trunk, e.g. with probe_mode(); "
-                                          f"got requires_grad on {[n for n in trainable if not n.startswith('head.')][:3]} ...")
+        grad = target is not None and torch.is_grad_enabled() and bool(trainable)
+        if grad:
             anchor = self.__dict__.get("_anchor")
             if anchor is None or anchor.device != x.device:
                 anchor = self.__dict__["_anchor"] = torch.zeros((), device=x.device, requires_grad=True)
+        if self._finetune and target is not None:
+            if grad:
+                return _FinetuneFn.apply(self, x, target, anchor)
+            with torch.no_grad():
+                loss, logits, _, _, _ = self._finetune_pass(x, target, want_grad=False)
+            return loss, logits
+        if grad:
+            if any(not n.startswith("head.") for n in trainable):
+                raise NotImplementedError("only the head is trainable on the MI355X path (linear probing): freeze the trunk, e.g. with probe_mode(), or "
+                                          f"train all of it with finetune_mode(); got requires_grad on {[n for n in trainable if not n.startswith('head.')][:3]} ...")
             return _ProbeFn.apply(self, x, target, anchor)
         with torch.no_grad():
             loss, logits, _, _ = self._head_pass(x, target, want_grad=False)

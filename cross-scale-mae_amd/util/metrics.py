@@ -59,3 +59,29 @@ def calc_metric(x, y, metric_name):
     name = metric_name.lower()
     name = {"ssd": "l2", "sad": "l1"}.get(name, name)
     return METRICS_DICT[name]["lambda"](x, y)
+
+
+def confusion_matrix(y_true, y_pred, num_classes=None):
+    """[K, K] int64 counts, rows = true class, columns = predicted class (numpy, on the host)."""
+    import numpy as np
+    y_true, y_pred = np.asarray(y_true).astype(np.int64).reshape(-1), np.asarray(y_pred).astype(np.int64).reshape(-1)
+    if num_classes is None:
+        num_classes = int(max(y_true.max(initial=-1), y_pred.max(initial=-1))) + 1
+    cm = np.zeros((num_classes, num_classes), dtype=np.int64)
+    np.add.at(cm, (y_true, y_pred), 1)
+    return cm
+
+
+def f1_scores(y_true, y_pred, num_classes=None):
+    """-> (macro F1, micro F1, per-class F1) as sklearn.metrics.f1_score(average="macro" / "micro" / None) computes them: the classes are the
+    labels that occur in y_true or y_pred, a class without predicted and without true samples in its denominator scores 0."""
+    import numpy as np
+    cm = confusion_matrix(y_true, y_pred, num_classes)
+    tp = np.diag(cm).astype(np.float64)
+    pred, true = cm.sum(0).astype(np.float64), cm.sum(1).astype(np.float64)
+    present = (pred + true) > 0
+    denom = pred + true          # 2 tp + fp + fn
+    per_class = np.where(denom > 0, 2.0 * tp / np.maximum(denom, 1.0), 0.0)[present]
+    macro = float(per_class.mean()) if per_class.size else 0.0
+    micro = float(2.0 * tp.sum() / max(denom.sum(), 1.0))
+    return macro, micro, per_class

@@ -344,6 +344,30 @@ int csmae_softmax_ce(long long N, int K, const float* logits, const long long* l
 int csmae_lars_step(int ntensors, const long long* table, float lr, float weight_decay, float momentum, float trust, float* norms, const float* gate,
                     void* stream);
 
+/* ---- end-to-end fine-tuning (main_finetune.py, engine_finetune.py; added within ABI version 7, csrc/finetune.hip).  No atomics: two runs give the
+ * same bits. */
+/* Reverse of csmae_probe_pool_fwd: recomputes the pooled row and its LayerNorm statistics from x [N, T, D] (fp32 or bf16), applies the LayerNorm
+ * backward to dfeat [N, D] and writes the WHOLE gradient dres [N, T, D] (the dtype of x): global_pool = 1: rows 1 .. T-1 get dpooled / (T - 1), row
+ * 0 zero; 0: row 0 gets the gradient, the others zero.  dgamma / dbeta [D] (+)= the sum over N in sample order (partial: 2 N D floats of scratch).
+ * x, dres 16-byte aligned, D % 4 == 0, D <= 4096; global_pool with T = 1 is refused. */
+int csmae_probe_pool_bwd(int dtype, int global_pool, long long N, int T, int D, const void* x, const float* dfeat, const float* gamma, float eps,
+                         void* dres, float* partial, float* dgamma, float* dbeta, int accumulate, void* stream);
+/* dx [N, D] = gscale dlogits [N, K] w [K, D] (gscale: nullable device scalar, 1 when absent) */
+int csmae_head_linear_dx(long long N, int D, int K, const float* dlogits, const float* w, const float* gscale, float* dx, void* stream);
+/* soft-target cross-entropy (timm SoftTargetCrossEntropy): loss[0] = mean_n sum_k -target[n, k] log_softmax(logits)[n, k]; dlogits (nullable) =
+ * gout (softmax sum_k target - target) / N (gout: nullable device scalar).  target: dense fp32 [N, K].  scratch: N floats. */
+int csmae_soft_ce(long long N, int K, const float* logits, const float* target, const float* gout, float* scratch, float* loss, float* dlogits,
+                  void* stream);
+/* dense targets [N, K] from labels [N] (int64), timm mixup_target: lam onehot(y[n], on, off) + (1 - lam) onehot(y[N-1-n], on, off) with
+ * off = smoothing / K, on = 1 - smoothing + off; lam = 1 is plain label smoothing.  A label outside [0, K) indexes nothing. */
+int csmae_mixup_target(long long N, int K, const long long* labels, float lam, float smoothing, float* target, void* stream);
+/* batch-mode mixing of x [N, C, H, W] fp32 with the flipped batch, out of place (out != x), N even.  cutmix = 0: out[n] = lam x[n] + (1 - lam)
+ * x[N-1-n]; 1: out[n] = x[n] with rows [yl, yh) x columns [xl, xh) copied from x[N-1-n] (lam unused). */
+int csmae_mixup_cutmix(int cutmix, long long N, int C, int H, int W, const float* x, float* out, float lam, int yl, int yh, int xl, int xh,
+                       void* stream);
+/* dpos [T, D] (+)= sum_n dres[n] for dres [N, T, D] fp32 or bf16, fp32 accumulation in sample order */
+int csmae_pos_embed_grad(int dtype, long long N, int T, int D, const void* dres, float* dpos, int accumulate, void* stream);
+
 
 /* ---- a stream confined to a subset of the compute units (ABI version 5).  The reference overlaps DDP's bucket all-reduces and autograd's
  * weight-gradient work with the main chain on CUDA streams that share every SM (main_pretrain.py:417-421); on MI355X a GEMM workgroup owns a
