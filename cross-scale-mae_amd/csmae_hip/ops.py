@@ -607,6 +607,16 @@ def augment_u8(src, meta, mean, inv_std, dst, st=None):
                                   st if st is not None else stream()), "csmae_augment_u8")
 
 
+def eval_u8(src, meta, mean, inv_std, dst, st=None):
+    """src [N, Hmax, Wmax, C] uint8, meta [N, 8] int32 {H, W, Hr, Wr, top, left, 0, 0} (util.gpu_input.eval_transform_params), dst [N, C, S, S]
+    fp32: the eval transform of util/datasets.py:140-158."""
+    N, Hmax, Wmax, C = src.shape
+    assert src.dtype == torch.uint8 and src.is_contiguous() and meta.dtype == torch.int32 and meta.shape == (N, 8) and dst.shape[:2] == (N, C)
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.shape[-1] == dst.shape[-2]
+    check(load().csmae_eval_u8(N, C, Hmax, Wmax, dst.shape[-1], _p(src), _p(meta), _p(mean), _p(inv_std), _p(dst),
+                               st if st is not None else stream()), "csmae_eval_u8")
+
+
 def cast_bf16(src, dst, st=None):
     check(load().csmae_cast_f32_to_bf16(src.numel(), _p(src), _p(dst), st if st is not None else stream()), "csmae_cast_f32_to_bf16")
 

@@ -430,6 +430,14 @@ __device__ __forceinline__ float cubic_aa(float x) {
 #define AUG_MAX_TAPS 96
 #define AUG_MAX_C 8
 #define AUG_WX_TAPS 24   // horizontal weights kept in LDS (24 KiB: several workgroups per CU); taps beyond are recomputed (scale > 5.5)
+// The pieces of ATen's weight set-up that the training and the eval kernel share.  Output o of an axis resampled at `scale = in / out`
+// has the centre c = scale * (o + 0.5), the window [int(c - sup + 0.5), int(c + sup + 0.5)) clipped to the input, and tap k of a window
+// that starts at `lo` weighs cubic_aa((k + lo - c + 0.5) * inv); the weights are renormalised over the clipped window.
+__device__ __forceinline__ void aa_support(float scale, float& sup, float& inv) {
+  sup = scale >= 1.f ? 2.f * scale : 2.f;
+  inv = scale >= 1.f ? 1.f / scale : 1.f;
+}
+__device__ __forceinline__ float aa_weight(int k, int lo, float c, float inv) { return cubic_aa((k + lo - c + 0.5f) * inv); }
 // One workgroup per (image, output row).  The normalised vertical weights live in LDS, each thread (output column) keeps its
 // normalised horizontal weights in LDS too (column-major: conflict-free), so the tap loop is one byte load + convert + fma per
 // channel.  Normalisation is applied once at the end: sum_k w_k (v_k / 255 - mean) / std = (sum_k w_k v_k) / (255 std) - mean / std
@@ -448,15 +456,16 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(int Crt, int Hmax, int 
   const int* mt = meta + n * 8;
   const int H = mt[0], W = mt[1], bi = mt[2], bj = mt[3], bh = mt[4], bw = mt[5], hf = mt[6], vf = mt[7];
   const float sy = (float)bh / (float)S, sx = (float)bw / (float)S;
-  const float supy = sy >= 1.f ? 2.f * sy : 2.f, invy = sy >= 1.f ? 1.f / sy : 1.f;
-  const float supx = sx >= 1.f ? 2.f * sx : 2.f, invx = sx >= 1.f ? 1.f / sx : 1.f;
+  float supy, invy, supx, invx;
+  aa_support(sy, supy, invy);
+  aa_support(sx, supx, invx);
   if (threadIdx.x == 0) {
     const float cy = sy * (oy + 0.5f);
     int lo = (int)(cy - supy + 0.5f); lo = lo < 0 ? 0 : lo;
     int hi = (int)(cy + supy + 0.5f); hi = hi > bh ? bh : hi;
     int nn = hi - lo; nn = nn > AUG_MAX_TAPS ? AUG_MAX_TAPS : nn;
     float tot = 0.f;
-    for (int k = 0; k < nn; ++k) { const float w = cubic_aa((k + lo - cy + 0.5f) * invy); wy[k] = w; tot += w; }
+    for (int k = 0; k < nn; ++k) { const float w = aa_weight(k, lo, cy, invy); wy[k] = w; tot += w; }
     for (int k = 0; k < nn; ++k) wy[k] /= tot;
     ylo_s = lo; yn_s = nn;
   }
@@ -470,7 +479,7 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(int Crt, int Hmax, int 
     int xhi = (int)(cx + supx + 0.5f); xhi = xhi > bw ? bw : xhi;
     int xn = xhi - xlo; xn = xn > AUG_MAX_TAPS ? AUG_MAX_TAPS : xn;
     float totx = 0.f;
-    for (int b = 0; b < xn; ++b) { const float w = cubic_aa((b + xlo - cx + 0.5f) * invx); if (b < AUG_WX_TAPS) wx[b][tid] = w; totx += w; }
+    for (int b = 0; b < xn; ++b) { const float w = aa_weight(b, xlo, cx, invx); if (b < AUG_WX_TAPS) wx[b][tid] = w; totx += w; }
     const float rtx = 1.f / totx;
     float acc[NC];
 #pragma unroll
@@ -483,7 +492,7 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(int Crt, int Hmax, int 
       const unsigned char* px = img + ((long long)yy * Wmax + x0) * C;
       const float wa = wy[a] * rtx;
       for (int b = 0; b < xn; ++b, px += xstep) {
-        const float w = wa * (b < AUG_WX_TAPS ? wx[b][tid] : cubic_aa((b + xlo - cx + 0.5f) * invx));
+        const float w = wa * (b < AUG_WX_TAPS ? wx[b][tid] : aa_weight(b, xlo, cx, invx));
 #pragma unroll
         for (int c = 0; c < NC; ++c) if (c < C) acc[c] = fmaf(w, (float)px[c], acc[c]);
       }
@@ -502,4 +511,90 @@ extern "C" int csmae_augment_u8(long long N, int C, int Hmax, int Wmax, int S, c
   else if (C == 4) hipLaunchKernelGGL((augment_u8_kernel<4>), grid, dim3(256), 0, st, C, Hmax, Wmax, S, src, meta, mean, inv_std, dst);
   else hipLaunchKernelGGL((augment_u8_kernel<0>), grid, dim3(256), 0, st, C, Hmax, Wmax, S, src, meta, mean, inv_std, dst);
   return csmae_check_launch("csmae_augment_u8");
+}
+
+// The reference's eval transform (util/datasets.py:140-158) on the GPU, the sibling of augment_u8_kernel:
+//   ToTensor -> Normalize(mean, std) -> Resize(int(S / crop_pct), bicubic, antialias) -> CenterCrop(S)
+// `meta[n] = {H, W, Hr, Wr, top, left, 0, 0}` comes from eval_transform_params on the host (torchvision's Resize(int) + CenterCrop
+// arithmetic): output pixel (oy, ox) is pixel (oy + top, ox + left) of the H x W -> Hr x Wr resize.  Same layout of src and dst and the
+// same workgroup shape as the training kernel.  The centre in * (2 o + 1) / (2 out) reaches ~1000 for elongated images, where fp32 keeps
+// only 1e-4 of its fraction: it is split into an integer part and a fraction in [0, 1), and every tap offset is taken from the
+// fraction alone.  The host refuses (before any launch) a resize that needs more than AUG_MAX_TAPS taps or whose in * 2 out leaves 31 bits.
+__device__ __forceinline__ void aa_centre_split(int in, int out, int o, int& ci, float& cf) {
+  const unsigned num = (unsigned)in * (unsigned)(2 * o + 1), den = 2u * (unsigned)out;
+  const unsigned q = num / den;
+  ci = (int)q;
+  cf = (float)(num - q * den) / (float)den;
+}
+__device__ __forceinline__ void aa_window_split(int ci, float cf, float sup, int in, int& lo, int& n) {
+  lo = ci + (int)floorf(cf - sup + 0.5f); lo = lo < 0 ? 0 : lo;
+  int hi = ci + (int)floorf(cf + sup + 0.5f); hi = hi > in ? in : hi;
+  n = hi - lo; n = n > AUG_MAX_TAPS ? AUG_MAX_TAPS : n;   // (keeps wy[] in bounds whatever meta holds; never taken after the host check)
+}
+template <int CT>  // CT = channel count known at compile time (3, 4) or 0 = any C <= 8
+__global__ __launch_bounds__(256) void eval_u8_kernel(int Crt, int Hmax, int Wmax, int S, const unsigned char* __restrict__ src,
+                                                      const int* __restrict__ meta, const float* __restrict__ mean,
+                                                      const float* __restrict__ inv_std, float* __restrict__ dst) {
+  __shared__ float wy[AUG_MAX_TAPS];
+  __shared__ float wx[AUG_WX_TAPS][256];
+  const int C = CT ? CT : Crt;
+  constexpr int NC = CT ? CT : AUG_MAX_C;
+  __shared__ int ylo_s, yn_s;
+  const long long n = blockIdx.x;
+  const int oy = blockIdx.y;
+  const int* mt = meta + n * 8;
+  const int H = mt[0] < Hmax ? mt[0] : Hmax, W = mt[1] < Wmax ? mt[1] : Wmax;   // no read leaves the image's slot of src
+  const int Hr = mt[2], Wr = mt[3], top = mt[4], left = mt[5];
+  float supy, invy, supx, invx;
+  aa_support((float)H / (float)Hr, supy, invy);
+  aa_support((float)W / (float)Wr, supx, invx);
+  if (threadIdx.x == 0) {
+    int ci, lo, nn; float cf;
+    aa_centre_split(H, Hr, oy + top, ci, cf);
+    aa_window_split(ci, cf, supy, H, lo, nn);
+    float tot = 0.f;
+    for (int k = 0; k < nn; ++k) { const float w = aa_weight(k, lo - ci, cf, invy); wy[k] = w; tot += w; }
+    for (int k = 0; k < nn; ++k) wy[k] /= tot;
+    ylo_s = lo; yn_s = nn;
+  }
+  __syncthreads();
+  const int ylo = ylo_s, yn = yn_s;
+  const unsigned char* img = src + n * (long long)Hmax * Wmax * C;
+  const int tid = threadIdx.x;
+  for (int ox = tid; ox < S; ox += blockDim.x) {
+    int ci, xlo, xn; float cx;
+    aa_centre_split(W, Wr, ox + left, ci, cx);
+    aa_window_split(ci, cx, supx, W, xlo, xn);
+    const int xr = xlo - ci;   // the window's start relative to the centre's integer part
+    float totx = 0.f;
+    for (int b = 0; b < xn; ++b) { const float w = aa_weight(b, xr, cx, invx); if (b < AUG_WX_TAPS) wx[b][tid] = w; totx += w; }
+    const float rtx = 1.f / totx;
+    float acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0.f;
+    for (int a = 0; a < yn; ++a) {
+      const unsigned char* px = img + ((long long)(ylo + a) * Wmax + xlo) * C;
+      const float wa = wy[a] * rtx;
+      for (int b = 0; b < xn; ++b, px += C) {
+        const float w = wa * (b < AUG_WX_TAPS ? wx[b][tid] : aa_weight(b, xr, cx, invx));
+#pragma unroll
+        for (int c = 0; c < NC; ++c) if (c < C) acc[c] = fmaf(w, (float)px[c], acc[c]);
+      }
+    }
+    // sum_k w_k (v_k / 255 - mean) / std = (sum_k w_k v_k - 255 mean) / (255 std): the weights sum to one
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (c < C) dst[((n * C + c) * S + oy) * (long long)S + ox] = (acc[c] - 255.f * mean[c]) * (inv_std[c] / 255.f);
+  }
+}
+extern "C" int csmae_eval_u8(long long N, int C, int Hmax, int Wmax, int S, const unsigned char* src, const int* meta, const float* mean,
+                             const float* inv_std, float* dst, void* stream) {
+  CSMAE_REQUIRE(N > 0 && C > 0 && C <= AUG_MAX_C && Hmax > 0 && Wmax > 0 && S > 0 && S <= 65535 && src && meta && mean && inv_std && dst,
+                "csmae_eval_u8: bad arguments (C <= 8, S <= 65535)");
+  dim3 grid((unsigned)N, (unsigned)S);
+  hipStream_t st = (hipStream_t)stream;
+  if (C == 3) hipLaunchKernelGGL((eval_u8_kernel<3>), grid, dim3(256), 0, st, C, Hmax, Wmax, S, src, meta, mean, inv_std, dst);
+  else if (C == 4) hipLaunchKernelGGL((eval_u8_kernel<4>), grid, dim3(256), 0, st, C, Hmax, Wmax, S, src, meta, mean, inv_std, dst);
+  else hipLaunchKernelGGL((eval_u8_kernel<0>), grid, dim3(256), 0, st, C, Hmax, Wmax, S, src, meta, mean, inv_std, dst);
+  return csmae_check_launch("csmae_eval_u8");
 }

@@ -5,9 +5,11 @@ choice, checkpoint layout and `log.jsonl`, with `engine_finetune.train_one_epoch
 
 Differences:
   * `--drop_path` defaults to 0.0 (the reference: 0.1) and a value above 0 raises: drop-path is not implemented in the MI355X blocks;
-  * `--dataset_type synthetic` (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches generated on the device; the fMoW /
-    Sentinel / EuroSAT readers of `util/datasets.py` need rasterio / fiona and are not wired (selecting them raises), so the augmentation
-    flags (`--aa`, `--color_jitter`, `--reprob`, ...) are parsed and unused;
+  * `--dataset_type rgb` (the default) reads the fMoW-RGB CSVs `--train_path` / `--test_path`: the loader workers only decode, the
+    training and the eval transform of `util/datasets.py` run on the device (`util/gpu_input.py`); `--dataset_type synthetic`
+    (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches generated on the device; the multi-band readers (Sentinel /
+    EuroSAT / ...) need rasterio / fiona and are not wired (selecting them raises); the augmentation flags (`--aa`, `--color_jitter`,
+    `--reprob`, ...) are parsed and unused, as the reference's fMoW-RGB dataset ignores them too;
   * `--model` defaults to `vit_base_patch16` (the reference's default `mae_vit_base` names no factory of `models_vit`);
     `--embed_dim / --depth / --num_heads` override a factory's geometry for small runs;
   * the model computes the criterion (soft-target cross-entropy under mixup, label-smoothed cross-entropy with `--smoothing`, otherwise plain
@@ -16,7 +18,7 @@ Differences:
     (WORLD_SIZE > 1 raises).
 
     python main_finetune.py --model vit_base_patch16 --finetune out/checkpoint-199.pth --transform_checkpoint_keys \\
-        --dataset_type synthetic --batch_size 128 --epochs 1
+        --dataset_type rgb --train_path train_62classes.csv --test_path val_62classes.csv --batch_size 128 --epochs 1
 """
 import argparse
 import datetime
@@ -32,7 +34,7 @@ import models_vit
 import util.lr_decay as lrd
 import util.misc as misc
 from engine_finetune import evaluate, train_one_epoch
-from main_linprobe import SyntheticLoader
+from main_linprobe import build_loaders
 from util.checkpoint_keys import to_vit_keys
 from util.misc import NativeScalerWithGradNormCount as NativeScaler
 from util.mixup import Mixup
@@ -62,7 +64,7 @@ def get_args_parser():
     p.add_argument("--layer_decay", type=float, default=0.75, help="layer-wise lr decay from ELECTRA/BEiT")
     p.add_argument("--min_lr", type=float, default=1e-6, metavar="LR")
     p.add_argument("--warmup_epochs", type=int, default=5, metavar="N")
-    # augmentation (parsed for compatibility: the synthetic loader augments nothing)
+    # augmentation (parsed for compatibility: neither loader reads them)
     p.add_argument("--color_jitter", type=float, default=None, metavar="PCT")
     p.add_argument("--aa", type=str, default="rand-m9-mstd0.5-inc1", metavar="NAME")
     p.add_argument("--smoothing", type=float, default=0.1, help="Label smoothing (default: 0.1)")
@@ -155,11 +157,7 @@ def main(args):
     np.random.seed(args.seed)
     if args.drop_path > 0:
         raise NotImplementedError(f"--drop_path {args.drop_path}: drop-path is not implemented in the MI355X blocks (the reference's default is 0.1; here 0.0)")
-    if args.dataset_type != "synthetic":
-        raise NotImplementedError(f"--dataset_type {args.dataset_type}: the reference's readers (util/datasets.py) depend on rasterio / fiona and are not "
-                                  "wired here; use --dataset_type synthetic or drive train_one_epoch / evaluate with your own iterable of (samples, labels)")
-    loader_train = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, args.synthetic_len, device, args.seed)
-    loader_val = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, max(1, args.synthetic_len // 4), device, args.seed)
+    loader_train, loader_val, n_val = build_loaders(args, device)
 
     mixup_fn = None
     if args.mixup > 0 or args.cutmix > 0.0 or args.cutmix_minmax is not None:
@@ -214,9 +212,8 @@ def main(args):
 
     if args.eval:
         stats = evaluate(loader_val, model, device, args)
-        n = len(loader_val) * args.batch_size
         acc5 = f"\n\tacc5: {stats['acc5']:.2f}%, " if "acc5" in stats else ""
-        print(f"Evaluation on {n} test images:\n\tacc1: {stats['acc1']:.2f}%{acc5}\n\tmacro_f1: {stats['macro_f1']:.2f}%, \n\tmicro_f1: {stats['micro_f1']:.2f}%")
+        print(f"Evaluation on {n_val} test images:\n\tacc1: {stats['acc1']:.2f}%{acc5}\n\tmacro_f1: {stats['macro_f1']:.2f}%, \n\tmicro_f1: {stats['micro_f1']:.2f}%")
         return stats
 
     print(f"Start training for {args.epochs} epochs")
@@ -229,7 +226,7 @@ def main(args):
                                 or epoch + 1 == args.epochs):
             misc.save_model(args=args, model=model, model_without_ddp=model, optimizer=optimizer, loss_scaler=loss_scaler, epoch=epoch)
         test_stats = evaluate(loader_val, model, device, args)
-        print(f"Accuracy of the network on the {len(loader_val) * args.batch_size} test images: {test_stats['acc1']:.1f}%")
+        print(f"Accuracy of the network on the {n_val} test images: {test_stats['acc1']:.1f}%")
         max_accuracy = max(max_accuracy, test_stats["acc1"])
         print(f"Max accuracy: {max_accuracy:.2f}%")
         log_stats.update({f"test_{k}": v for k, v in test_stats.items()})

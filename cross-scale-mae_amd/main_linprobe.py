@@ -4,8 +4,10 @@ names, types and defaults), its model factory call, LR scaling, probe head (Batc
 :515-525), LARS, checkpoint layout and `log.jsonl`, and a `train_one_epoch` / `evaluate` pair after `engine_finetune.py`.
 
 Differences:
-  * `--dataset_type synthetic` (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches with fixed labels generated on the
-    device; the fMoW / Sentinel / EuroSAT readers of `util/datasets.py` need rasterio / fiona and are not wired (selecting them raises);
+  * `--dataset_type rgb` (the default) reads the fMoW-RGB CSVs `--train_path` / `--test_path`: the loader workers only decode, the
+    training and the eval transform of `util/datasets.py` run on the device (`util/gpu_input.py`); `--dataset_type synthetic`
+    (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches with fixed labels generated on the device; the multi-band
+    readers (Sentinel / EuroSAT / ...) need rasterio / fiona and are not wired (selecting them raises);
   * `--model` defaults to `vit_base_patch16` (the reference's default `mae_vit_base` names no factory of `models_vit`);
     `--embed_dim / --depth / --num_heads` override a factory's geometry for small runs;
   * the per-iteration loss and the top-1 / top-5 hit counts stay on the device and are drained every `--print_freq` iterations; a
@@ -15,7 +17,7 @@ Differences:
   * mixup, layer decay, drop-path, F1 / mIoU, W&B / TensorBoard and multi-GPU probing are out of scope (WORLD_SIZE > 1 raises).
 
     python main_linprobe.py --model vit_base_patch16 --finetune out/checkpoint-199.pth --transform_checkpoint_keys \\
-        --dataset_type synthetic --batch_size 128 --epochs 1
+        --dataset_type rgb --train_path train_62classes.csv --test_path val_62classes.csv --batch_size 128 --epochs 1
 """
 import argparse
 import datetime
@@ -58,6 +60,8 @@ def get_args_parser():
     p.add_argument("--cls_token", action="store_false", dest="global_pool", help="Use class token instead of global pool for classification")
     p.add_argument("--transform_checkpoint_keys", action="store_true", default=False,
                    help="map the pre-training model's keys to ViT keys (applied by itself when the checkpoint holds encoder_pos_embed)")
+    p.add_argument("--train_path", default="./train_64.csv", type=str, help="Train .csv path")
+    p.add_argument("--test_path", default="/data2/HDD_16TB/fmow-rgb-preproc/val_224.csvv", type=str, help="Test .csv path")
     p.add_argument("--dataset_type", type=str, default="rgb", choices=["rgb", "sentinel", "euro_sat", "naip", "smart", "spacenetv1", "resisc45", "synthetic"])
     p.add_argument("--nb_classes", default=62, type=int, help="number of the classification types")
     p.add_argument("--output_dir", type=str, default=None)
@@ -68,6 +72,7 @@ def get_args_parser():
     p.add_argument("--save_every", type=int, default=1)
     p.add_argument("--start_epoch", default=0, type=int, metavar="N")
     p.add_argument("--eval", action="store_true", help="Perform evaluation only")
+    p.add_argument("--num_workers", type=int, default=10, help="decoding worker processes of the rgb loader")
     # ---- additive flags of the MI355X build
     p.add_argument("--synthetic_len", type=int, default=64, help="iterations per epoch of the synthetic loader (a quarter of it for evaluation)")
     p.add_argument("--input_channels", type=int, default=3, help="bands of the synthetic loader / model")
@@ -93,6 +98,25 @@ class SyntheticLoader:
     def __iter__(self):
         for _ in range(self.length):
             yield self.samples, self.targets
+
+
+def build_loaders(args, device):
+    """-> (train loader or None under --eval, eval loader, number of eval images) for --dataset_type synthetic / rgb; shared with
+    main_finetune.py.  Any other type raises NotImplementedError; a missing CSV raises the FileNotFoundError of its read."""
+    if args.dataset_type == "synthetic":
+        loader_train = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, args.synthetic_len, device, args.seed)
+        loader_val = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, max(1, args.synthetic_len // 4), device, args.seed)
+        return loader_train, loader_val, len(loader_val) * args.batch_size
+    if args.dataset_type != "rgb":
+        raise NotImplementedError(f"--dataset_type {args.dataset_type}: the reference's multi-band readers (util/datasets.py) depend on rasterio / fiona "
+                                  "and are not wired here; use --dataset_type rgb / synthetic or drive train_one_epoch / evaluate with your own "
+                                  "iterable of (samples, labels)")
+    if args.input_channels != 3:
+        raise ValueError(f"--dataset_type rgb decodes 3 bands: --input_channels {args.input_channels} does not fit")
+    from util.gpu_input import build_fmow_rgb_loader
+    loader_train = None if args.eval else build_fmow_rgb_loader(args.train_path, True, args, device)
+    loader_val = build_fmow_rgb_loader(args.test_path, False, args, device)
+    return loader_train, loader_val, len(loader_val.dataset)
 
 
 def _autocast(device):
@@ -193,11 +217,7 @@ def main(args):
     device = torch.device(args.device)
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
-    if args.dataset_type != "synthetic":
-        raise NotImplementedError(f"--dataset_type {args.dataset_type}: the reference's readers (util/datasets.py) depend on rasterio / fiona and are not "
-                                  "wired here; use --dataset_type synthetic or drive train_one_epoch / evaluate with your own iterable of (samples, labels)")
-    loader_train = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, args.synthetic_len, device, args.seed)
-    loader_val = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, max(1, args.synthetic_len // 4), device, args.seed)
+    loader_train, loader_val, n_val = build_loaders(args, device)
 
     geometry = {k: getattr(args, k) for k in ("embed_dim", "depth", "num_heads") if getattr(args, k) is not None}
     model = models_vit.__dict__[args.model](patch_size=args.patch_size, img_size=args.input_size, in_chans=args.input_channels,
@@ -229,7 +249,7 @@ def main(args):
 
     if args.eval:
         stats = evaluate(loader_val, model, device, args)
-        print(f"Evaluation on {len(loader_val) * args.batch_size} test images:\n\tacc1: {stats['acc1']:.2f}%\n\tacc5: {stats['acc5']:.2f}%")
+        print(f"Evaluation on {n_val} test images:\n\tacc1: {stats['acc1']:.2f}%\n\tacc5: {stats['acc5']:.2f}%")
         return stats
 
     print(f"Start training for {args.epochs} epochs")

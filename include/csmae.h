@@ -293,6 +293,11 @@ int csmae_loss_finalize(long long per_view, int views, const float* rowloss, con
  * (box in the coordinates of the flipped image; drawn on the host in torchvision's RNG order), dst [N, C, S, S] fp32. */
 int csmae_augment_u8(long long N, int C, int Hmax, int Wmax, int S, const unsigned char* src, const int* meta, const float* mean,
                      const float* inv_std, float* dst, void* stream);
+/* the eval transform (util/datasets.py:140-158): ToTensor, Normalize, Resize(int(S / crop_pct), bicubic, antialias), CenterCrop(S).
+ * Same src / dst layout; meta [N, 8] int32 = {H, W, Hr, Wr, top, left, 0, 0}: output pixel (oy, ox) is pixel (oy + top, ox + left) of the
+ * H x W -> Hr x Wr resize.  The host (util/gpu_input.py eval_transform_params) computes meta and refuses sizes the kernel cannot hold. */
+int csmae_eval_u8(long long N, int C, int Hmax, int Wmax, int S, const unsigned char* src, const int* meta, const float* mean,
+                  const float* inv_std, float* dst, void* stream);
 
 /* ---- optimizer side (main_pretrain.py:426-427 torch.optim.AdamW; util/misc.py:314 backward products) */
 /* gate (nullable device scalar): the update is skipped as a whole when it is not finite — engine_pretrain.py:56-58 raises on a
