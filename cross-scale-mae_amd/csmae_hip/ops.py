@@ -629,7 +629,7 @@ def colsum(x, out, st=None):
     check(load().csmae_colsum(dt(x), x.shape[0], x.shape[1], _p(x), x.stride(0), _p(out), st if st is not None else stream()), "csmae_colsum")
 
 
-# ---- linear probing (csrc/linprobe.hip): everything behind the last transformer block, fp32
+# ---- linear probing (csrc/classify.hip): everything behind the last transformer block, fp32
 def _f32c(*ts):
     for t in ts:
         assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), "linear-probe kernels take contiguous fp32 tensors"
@@ -708,7 +708,7 @@ def lars_step(table, norms, lr, weight_decay, momentum, trust_coefficient, gate=
                                  st if st is not None else stream()), "csmae_lars_step")
 
 
-# ---- end-to-end fine-tuning (csrc/finetune.hip)
+# ---- end-to-end fine-tuning (csrc/classify.hip)
 def probe_pool_bwd(x, dfeat, gamma, dres, dgamma, dbeta, global_pool, eps=1e-6, accumulate=False, partial=None, st=None):
     """Reverse of probe_pool_fwd: dres [N, T, D] (the dtype of x, every element written) from dfeat [N, D]; dgamma / dbeta [D] (+)= over the batch."""
     N, T, D = x.shape

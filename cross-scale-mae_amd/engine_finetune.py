@@ -4,7 +4,6 @@ Differences: the model computes the criterion itself (`model(samples, targets)`;
 used: main_finetune.py sets `model.smoothing` / the mixup targets instead); `max_norm` 0 or None means no clipping; losses stay on the device and are drained every `args.print_freq` iterations (a non-finite loss raises at
 that drain, FusedAdamW skips on the device every update whose loss was not finite); macro / micro F1 come from a numpy confusion matrix
 (util.metrics.f1_scores); W&B / TensorBoard logging and the mIoU (`use_psa`) branch are not wired."""
-import math
 from typing import Iterable, Optional
 
 import numpy as np
@@ -12,12 +11,8 @@ import torch
 
 import util.lr_sched as lr_sched
 import util.misc as misc
+from util.downstream import PendingLosses, autocast
 from util.metrics import f1_scores
-
-
-def _autocast(device):
-    import contextlib
-    return torch.autocast("cuda", dtype=torch.bfloat16) if torch.device(device).type == "cuda" else contextlib.nullcontext()
 
 
 def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, optimizer: torch.optim.Optimizer, device: torch.device, epoch: int,
@@ -31,19 +26,7 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
     accum_iter, print_freq = args.accum_iter, getattr(args, "print_freq", 20)
     optimizer.zero_grad()
     n_iters = len(data_loader)
-    pending = []   # (device loss, largest group lr)
-
-    def drain():
-        if not pending:
-            return
-        values = torch.stack([p[0].detach().float().reshape(()) for p in pending]).tolist()
-        for value, (_, lr) in zip(values, pending):
-            if not math.isfinite(value):
-                print("Loss is {}, stopping training".format(value))
-                raise ValueError(f"Loss is {value}, stopping training")
-            metric_logger.update(loss=value)
-            metric_logger.update(lr=lr)
-        pending.clear()
+    pending = PendingLosses()   # (with the largest group lr)
 
     for it, (samples, targets) in enumerate(metric_logger.log_every(data_loader, print_freq, header)):
         if it % accum_iter == 0:   # a per-iteration (not per-epoch) schedule
@@ -51,16 +34,16 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
         samples, targets = samples.to(device, non_blocking=True), targets.to(device, non_blocking=True)
         if mixup_fn is not None:
             samples, targets = mixup_fn(samples, targets)
-        with _autocast(device):
+        with autocast(device):
             loss, _ = model(samples, targets)
-        pending.append((loss, max(g["lr"] for g in optimizer.param_groups)))
+        pending.append(loss, max(g["lr"] for g in optimizer.param_groups))
         loss_scaler(loss / accum_iter, optimizer, clip_grad=max_norm or None, parameters=model.parameters(), create_graph=False,
                     update_grad=(it + 1) % accum_iter == 0)
         if (it + 1) % accum_iter == 0:
             optimizer.zero_grad()
         if it % print_freq == 0 or it == n_iters - 1:
-            drain()   # exactly the iterations on which log_every prints the meters
-    drain()
+            pending.drain(metric_logger)   # exactly the iterations on which log_every prints the meters
+    pending.drain(metric_logger)
     metric_logger.synchronize_between_processes()
     print("Averaged stats:", metric_logger)
     return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
@@ -78,7 +61,7 @@ def evaluate(data_loader, model, device, args=None, ignore_index=-9999):
     losses, true_labels, predict = [], [], []
     for batch in data_loader:
         images, target = batch[0].to(device, non_blocking=True), batch[-1].to(device, non_blocking=True)
-        with _autocast(device):
+        with autocast(device):
             loss, output = model(images, target)
         losses.append(loss.reshape(()) * images.shape[0])
         true_labels.append(target)

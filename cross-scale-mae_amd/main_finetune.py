@@ -25,24 +25,18 @@ import datetime
 import json
 import os
 import time
-from pathlib import Path
 
 import numpy as np
 import torch
 
-import models_vit
 import util.lr_decay as lrd
 import util.misc as misc
 from engine_finetune import evaluate, train_one_epoch
-from main_linprobe import build_loaders
 from util.checkpoint_keys import to_vit_keys
+from util.downstream import build_loaders, build_model, make_output_dir, nullable_string, scale_lr
 from util.misc import NativeScalerWithGradNormCount as NativeScaler
 from util.mixup import Mixup
 from util.pos_embed import interpolate_pos_embed
-
-
-def nullable_string(val):
-    return val if val else None
 
 
 def get_args_parser():
@@ -167,23 +161,14 @@ def main(args):
     else:
         print("Not using mixup")
 
-    geometry = {k: getattr(args, k) for k in ("embed_dim", "depth", "num_heads") if getattr(args, k) is not None}
-    model = models_vit.__dict__[args.model](patch_size=args.patch_size, img_size=args.input_size, in_chans=args.input_channels,
-                                            num_classes=args.nb_classes, drop_path_rate=args.drop_path, global_pool=args.global_pool, **geometry)
+    model = build_model(args, args.drop_path)
     if args.finetune and not args.eval:
         load_pretrained(model, args.finetune, args.transform_checkpoint_keys)
     model.finetune_mode()
     model.to(device)
     print(f"Model = {model}")
 
-    batch_size_eff = args.batch_size * args.accum_iter
-    print("accumulate grad iterations: %d" % args.accum_iter)
-    print("effective batch size: %d" % batch_size_eff)
-    print("number of params (M): %.2f" % (sum(p.numel() for p in model.parameters() if p.requires_grad) / 1.0e6))
-    if args.lr is None:
-        args.lr = args.blr * batch_size_eff / 256
-    print("base lr: %.2e" % (args.lr * 256 / batch_size_eff))
-    print("actual lr: %.2e" % args.lr)
+    scale_lr(args, model)
 
     # layer-wise lr decay (lrd) groups, stepped by one fused kernel launch each
     from csmae_hip.optim import FusedAdamW
@@ -205,10 +190,7 @@ def main(args):
     model_name = "_".join([args.model, f"i{args.input_size}-p{args.patch_size}", f"e{args.epochs}-we{args.warmup_epochs}", f"b{args.batch_size}-a{args.accum_iter}",
                            f"-lr{args.lr}", f"-mixup{args.mixup}", f"-cutmix{args.cutmix}", f"-smoothing{args.smoothing}",
                            "_cls_only" if not args.global_pool else "_global_pool", "finetune"])
-    if args.output_dir is None:
-        args.output_dir = os.path.join(args.output_dir_base or ".", f"out_{model_name}")
-    print(f"Output directory: {args.output_dir}")
-    Path(args.output_dir).mkdir(parents=True, exist_ok=True)
+    make_output_dir(args, model_name)
 
     if args.eval:
         stats = evaluate(loader_val, model, device, args)

@@ -22,23 +22,17 @@ Differences:
 import argparse
 import datetime
 import json
-import math
 import os
 import time
-from pathlib import Path
 
 import numpy as np
 import torch
 
-import models_vit
 import util.lr_sched as lr_sched
 import util.misc as misc
 from util.checkpoint_keys import to_vit_keys
+from util.downstream import PendingLosses, autocast, build_loaders, build_model, make_output_dir, nullable_string, scale_lr
 from util.lars import LARS
-
-
-def nullable_string(val):
-    return val if val else None
 
 
 def get_args_parser():
@@ -83,47 +77,6 @@ def get_args_parser():
     return p
 
 
-class SyntheticLoader:
-    """In-memory repeat loader: (samples [N, C, S, S] ~ N(0, 1), labels [N] int64) on `device`, the same batch every iteration."""
-
-    def __init__(self, batch, channels, size, classes, length, device, seed):
-        g = torch.Generator(device=device).manual_seed(seed)
-        self.samples = torch.randn(batch, channels, size, size, device=device, generator=g)
-        self.targets = torch.randint(0, classes, (batch,), device=device, generator=g)
-        self.length = length
-
-    def __len__(self):
-        return self.length
-
-    def __iter__(self):
-        for _ in range(self.length):
-            yield self.samples, self.targets
-
-
-def build_loaders(args, device):
-    """-> (train loader or None under --eval, eval loader, number of eval images) for --dataset_type synthetic / rgb; shared with
-    main_finetune.py.  Any other type raises NotImplementedError; a missing CSV raises the FileNotFoundError of its read."""
-    if args.dataset_type == "synthetic":
-        loader_train = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, args.synthetic_len, device, args.seed)
-        loader_val = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, max(1, args.synthetic_len // 4), device, args.seed)
-        return loader_train, loader_val, len(loader_val) * args.batch_size
-    if args.dataset_type != "rgb":
-        raise NotImplementedError(f"--dataset_type {args.dataset_type}: the reference's multi-band readers (util/datasets.py) depend on rasterio / fiona "
-                                  "and are not wired here; use --dataset_type rgb / synthetic or drive train_one_epoch / evaluate with your own "
-                                  "iterable of (samples, labels)")
-    if args.input_channels != 3:
-        raise ValueError(f"--dataset_type rgb decodes 3 bands: --input_channels {args.input_channels} does not fit")
-    from util.gpu_input import build_fmow_rgb_loader
-    loader_train = None if args.eval else build_fmow_rgb_loader(args.train_path, True, args, device)
-    loader_val = build_fmow_rgb_loader(args.test_path, False, args, device)
-    return loader_train, loader_val, len(loader_val.dataset)
-
-
-def _autocast(device):
-    import contextlib
-    return torch.autocast("cuda", dtype=torch.bfloat16) if torch.device(device).type == "cuda" else contextlib.nullcontext()
-
-
 def train_one_epoch(model, data_loader, optimizer, device, epoch, args=None, log_writer=None):
     """engine_finetune.py's epoch for the probe: LR schedule per iteration, loss / lr / acc1 / acc5 meters, gradient accumulation.  The
     model computes the cross-entropy itself (`model(samples, targets)`); loss and hit counts are read every `print_freq` iterations."""
@@ -134,40 +87,25 @@ def train_one_epoch(model, data_loader, optimizer, device, epoch, args=None, log
     accum_iter, print_freq = args.accum_iter, getattr(args, "print_freq", 20)
     optimizer.zero_grad(set_to_none=False)
     n_iters = len(data_loader)
-    pending = []   # (device loss, lr)
+    pending = PendingLosses()
     gate = None
     model.drain_counts()
-
-    def drain():
-        if not pending:
-            return
-        values = torch.stack([p[0].detach().float().reshape(()) for p in pending]).tolist()
-        top1, top5, seen = model.drain_counts()
-        for value, (_, lr) in zip(values, pending):
-            if not math.isfinite(value):
-                print(f"Loss is {value}, stopping training")
-                raise ValueError(f"Loss is {value}, stopping training")
-            metric_logger.update(loss=value)
-            metric_logger.update(lr=lr)
-        metric_logger.meters["acc1"].update(100.0 * top1 / seen, n=seen)
-        metric_logger.meters["acc5"].update(100.0 * top5 / seen, n=seen)
-        pending.clear()
 
     for it, (samples, targets) in enumerate(metric_logger.log_every(data_loader, print_freq, header)):
         if it % accum_iter == 0:
             lr_sched.adjust_learning_rate(optimizer, it / n_iters + epoch, args)
         samples, targets = samples.to(device, non_blocking=True), targets.to(device, non_blocking=True)
-        with _autocast(device):
+        with autocast(device):
             loss, _ = model(samples, targets)
-        pending.append((loss, optimizer.param_groups[0]["lr"]))
+        pending.append(loss, optimizer.param_groups[0]["lr"])
         gate = loss.detach().reshape(1) if it % accum_iter == 0 else gate + loss.detach().reshape(1)   # the update's losses, summed
         (loss / accum_iter).backward()
         if (it + 1) % accum_iter == 0:
             optimizer.step(gate=gate)
             optimizer.zero_grad(set_to_none=False)
         if it % print_freq == 0 or it == n_iters - 1:
-            drain()   # exactly the iterations on which log_every prints the meters
-    drain()
+            pending.drain(metric_logger, model.drain_counts)   # exactly the iterations on which log_every prints the meters
+    pending.drain(metric_logger, model.drain_counts)
     metric_logger.synchronize_between_processes()
     print("Averaged stats:", metric_logger)
     return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
@@ -181,7 +119,7 @@ def evaluate(data_loader, model, device, args=None):
     losses = []
     for samples, targets in data_loader:
         samples, targets = samples.to(device, non_blocking=True), targets.to(device, non_blocking=True)
-        with _autocast(device):
+        with autocast(device):
             loss, _ = model(samples, targets)
         losses.append(loss * samples.shape[0])
     top1, top5, seen = model.drain_counts()
@@ -219,33 +157,21 @@ def main(args):
     np.random.seed(args.seed)
     loader_train, loader_val, n_val = build_loaders(args, device)
 
-    geometry = {k: getattr(args, k) for k in ("embed_dim", "depth", "num_heads") if getattr(args, k) is not None}
-    model = models_vit.__dict__[args.model](patch_size=args.patch_size, img_size=args.input_size, in_chans=args.input_channels,
-                                            num_classes=args.nb_classes, drop_path_rate=0.0, global_pool=args.global_pool, **geometry)
+    model = build_model(args)
     if args.finetune and not args.eval:
         load_pretrained(model, args.finetune, args.transform_checkpoint_keys)
     model.probe_mode()
     model.to(device)
     print(f"Model = {model}")
 
-    batch_size_eff = args.batch_size * args.accum_iter
-    print("accumulate grad iterations: %d" % args.accum_iter)
-    print("effective batch size: %d" % batch_size_eff)
-    print("number of params (M): %.2f" % (sum(p.numel() for p in model.parameters() if p.requires_grad) / 1.0e6))
-    if args.lr is None:
-        args.lr = args.blr * batch_size_eff / 256
-    print("base lr: %.2e" % (args.lr * 256 / batch_size_eff))
-    print("actual lr: %.2e" % args.lr)
+    scale_lr(args, model)
     optimizer = LARS(model.head.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     print(optimizer)
     misc.load_model(args=args, model_without_ddp=model, optimizer=optimizer, loss_scaler=None)
 
     model_name = "_".join([args.model, f"i{args.input_size}-p{args.patch_size}", f"e{args.epochs}-we{args.warmup_epochs}",
                            f"b{args.batch_size}-a{args.accum_iter}", f"lr{args.lr}", "_global_pool" if args.global_pool else "_cls_only", "linprobe"])
-    if args.output_dir is None:
-        args.output_dir = os.path.join(args.output_dir_base or ".", f"out_{model_name}")
-    print(f"Output directory: {args.output_dir}")
-    Path(args.output_dir).mkdir(parents=True, exist_ok=True)
+    make_output_dir(args, model_name)
 
     if args.eval:
         stats = evaluate(loader_val, model, device, args)

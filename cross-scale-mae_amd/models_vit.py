@@ -4,11 +4,11 @@ loads with strict=False leaving only `head.*` (and `fc_norm.*` under global pool
 
 * the trunk is the pre-training encoder forward (`csmae_hip.Engine.encode_stream` at mask_ratio 0 with an increasing noise ramp, so the
   token order is the identity): the resident / streaming attention kernels, bf16 MFMA under autocast, exact fp32 otherwise;
-* pooling + final norm, the probe's BatchNorm1d, the classifier, cross-entropy with top-1 / top-5 counts run in csrc/linprobe.hip.
+* pooling + final norm, the probe's BatchNorm1d, the classifier, cross-entropy with top-1 / top-5 counts run in csrc/classify.hip.
 
 Probe mode (main_linprobe.py:515-525) trains only the head: `loss.backward()` fills `head.1.weight.grad` / `head.1.bias.grad` through one
 coarse autograd node.  Fine-tune mode (`finetune_mode()`, main_finetune.py) trains everything: head, final norm and trunk share one flat
-buffer, and `loss.backward()` runs the head's backward of csrc/finetune.hip and `Engine.backward_stream`.  A model in neither mode refuses
+buffer, and `loss.backward()` runs the head's backward of csrc/classify.hip and `Engine.backward_stream`.  A model in neither mode refuses
 trunk gradients; dropout / drop-path > 0 is not implemented and raises."""
 from functools import partial
 
@@ -40,14 +40,20 @@ class _TrunkView:
 _STUB_DD = 8   # width of the decoder slots of the trunk view
 
 
-class _ProbeFn(torch.autograd.Function):
-    """One autograd node for trunk + head + loss: backward = the classifier's weight / bias gradient kernel, written into the `.grad`
-    tensors.  The only differentiable input is a zero-dim anchor (see models_mae.MAE_ViT_Baseline._StepFn)."""
+class _HeadFn(torch.autograd.Function):
+    """One autograd node for trunk + head + loss.  The only differentiable input is a zero-dim anchor (see
+    models_mae.MAE_ViT_Baseline._StepFn).  Probe mode: backward = the classifier's weight / bias gradient kernel, written into the `.grad`
+    tensors.  Fine-tune mode: classifier dW / db and dX, pooling + final-norm backward into the residual-stream gradient, then the trunk's
+    reverse pass (Engine.backward_stream); every gradient lands in the flat buffer, whose views become the `.grad`s.  A backward into
+    existing gradients accumulates."""
 
     @staticmethod
     def forward(ctx, model, x, target, anchor):
-        loss, logits, fbn, dlogits = model._head_pass(x, target, want_grad=True)
-        ctx.model, ctx.fbn, ctx.dlogits = model, fbn, dlogits
+        loss, logits, fbn, dlogits = model._pass(x, target, want_grad=True)
+        ctx.model, ctx.fbn, ctx.dlogits, ctx.eng = model, fbn, dlogits, None
+        if model._finetune:
+            ctx.eng = model._engine(x)
+            ctx.gen, ctx.loss = ctx.eng.gen, loss.detach()   # (not the output itself: no cycle through its grad_fn)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(logits)
         return loss, logits
@@ -56,33 +62,16 @@ class _ProbeFn(torch.autograd.Function):
     def backward(ctx, gloss, glogits):
         if gloss is not None:
             from csmae_hip import ops
+            gscale = gloss.detach().reshape(1).to(torch.float32).contiguous()
+            if ctx.eng is not None:
+                ctx.model._finetune_backward(ctx.eng, ctx.gen, ctx.fbn, ctx.dlogits, ctx.loss, gscale)
+                return (None,) * 4
             lin = ctx.model._linear()
             had = lin.weight.grad is not None or (lin.bias is not None and lin.bias.grad is not None)
             for p in (lin.weight, lin.bias):
                 if p is not None and p.grad is None:
                     p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            ops.head_linear_bwd(ctx.dlogits, ctx.fbn, lin.weight.grad, None if lin.bias is None else lin.bias.grad, accumulate=had,
-                                gscale=gloss.detach().reshape(1).to(torch.float32).contiguous())
-        return (None,) * 4
-
-
-class _FinetuneFn(torch.autograd.Function):
-    """One autograd node for trunk + head + loss in fine-tune mode.  backward = classifier dW / db and dX, pooling + final-norm backward into the
-    residual-stream gradient, then the trunk's reverse pass (Engine.backward_stream); every gradient lands in the flat buffer, whose views
-    become the `.grad`s.  A backward into existing gradients accumulates."""
-
-    @staticmethod
-    def forward(ctx, model, x, target, anchor):
-        loss, logits, eng, feat, dlogits = model._finetune_pass(x, target, want_grad=True)
-        ctx.model, ctx.eng, ctx.gen, ctx.feat, ctx.dlogits, ctx.loss = model, eng, eng.gen, feat, dlogits, loss.detach()   # (not the output itself: no cycle through its grad_fn)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(logits)
-        return loss, logits
-
-    @staticmethod
-    def backward(ctx, gloss, glogits):
-        if gloss is not None:
-            ctx.model._finetune_backward(ctx.eng, ctx.gen, ctx.feat, ctx.dlogits, ctx.loss, gloss.detach().reshape(1).to(torch.float32).contiguous())
+            ops.head_linear_bwd(ctx.dlogits, ctx.fbn, lin.weight.grad, None if lin.bias is None else lin.bias.grad, accumulate=had, gscale=gscale)
         return (None,) * 4
 
 
@@ -224,59 +213,48 @@ class VisionTransformer(nn.Module):
         ops.probe_pool_fwd(tokens, norm.weight.detach(), norm.bias.detach(), feat, self.global_pool, eps=norm.eps)
         return feat
 
-    def _head_pass(self, x, target, want_grad):
+    def _pass(self, x, target, want_grad):
+        """Trunk, pooling + final norm, the probe's BatchNorm, classifier, criterion.  `target`: int64 labels [N] (cross-entropy with the top-1 /
+        top-5 counters; in fine-tune mode label-smoothed by `self.smoothing` while training) or, in fine-tune mode only, dense float targets
+        [N, K] (soft-target cross-entropy); None: logits alone.
+        -> loss, logits, the classifier's input (fine-tune mode: the model's feat buffer; else a fresh tensor), dlogits (for a unit upstream
+        gradient; None unless want_grad)."""
         from csmae_hip import ops
-        feat = self._features(x)
-        N, D, K = feat.shape[0], self.embed_dim, self.num_classes
+        ft = self._finetune
+        feat = self._features(x, training=ft and want_grad)
+        N, D, K, dev = feat.shape[0], self.embed_dim, self.num_classes, feat.device
         lin = self._linear()
         if isinstance(self.head, nn.Sequential):
             bn = self.head[0]
             training = bn.training or bn.running_mean is None
-            fbn = torch.empty(N, D, device=feat.device, dtype=torch.float32)
+            fbn = torch.empty(N, D, device=dev, dtype=torch.float32)
             ops.bn1d_fwd(feat, fbn, bn.running_mean, bn.running_var, bn.num_batches_tracked, eps=bn.eps, momentum=bn.momentum, training=training)
         else:
-            fbn = feat.clone()
-        logits = torch.empty(N, K, device=feat.device, dtype=torch.float32)
+            fbn = feat if ft else feat.clone()
+        logits = torch.empty(N, K, device=dev, dtype=torch.float32)
         ops.head_linear_fwd(fbn, lin.weight.detach(), None if lin.bias is None else lin.bias.detach(), logits)
         if target is None:
             return None, logits, fbn, None
-        if target.shape != (N,) or target.dtype != torch.int64 or target.device != feat.device:
+        hard = target.dtype == torch.int64 and target.shape == (N,)
+        if ft:
+            if target.device != dev:
+                raise ValueError("target must live on the model's device")
+            if not hard and not (target.is_floating_point() and target.shape == (N, K)):
+                raise ValueError(f"target must be int64 labels of shape ({N},) or dense float targets of shape ({N}, {K})")
+        elif not hard or target.device != dev:
             raise ValueError(f"target must be an int64 tensor of shape ({N},) on the model's device")
-        loss = torch.empty(1, device=feat.device, dtype=torch.float32)
-        dlogits = torch.empty(N, K, device=feat.device, dtype=torch.float32) if want_grad else None
-        ops.softmax_ce(logits, target.contiguous(), loss, dlogits=dlogits, counts=self.hit_counts(), accumulate_counts=True,
-                       scratch=self._buf("ce_scratch", (3 * N,)))
-        self._seen += N
-        return loss.reshape(()), logits, fbn, dlogits
-
-    def _finetune_pass(self, x, target, want_grad):
-        """Fine-tune mode: trunk, pooling + final norm, classifier, criterion.  `target`: int64 labels [N] (cross-entropy with the top-1 / top-5
-        counters; label-smoothed by `self.smoothing` while training) or dense float targets [N, K] (soft-target cross-entropy).
-        -> loss, logits, engine, feat, dlogits (for a unit upstream gradient; None unless want_grad)."""
-        from csmae_hip import ops
-        feat = self._features(x, training=want_grad)
-        eng = self._engine(x)
-        N, K, dev = feat.shape[0], self.num_classes, feat.device
-        logits = torch.empty(N, K, device=dev, dtype=torch.float32)
-        ops.head_linear_fwd(feat, self.head.weight.detach(), None if self.head.bias is None else self.head.bias.detach(), logits)
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         dlogits = torch.empty(N, K, device=dev, dtype=torch.float32) if want_grad else None
-        if target.device != dev:
-            raise ValueError("target must live on the model's device")
-        if target.dtype == torch.int64 and target.shape == (N,):
-            smoothing = float(self.smoothing) if self.training else 0.0
-            if smoothing > 0.0:   # LabelSmoothingCrossEntropy(s) = soft-target cross-entropy on the smoothed one-hot rows
-                dense = ops.mixup_target(target.contiguous(), self._buf("dense_target", (N, K)), lam=1.0, smoothing=smoothing)
-                ops.soft_ce(logits, dense, loss, dlogits=dlogits, scratch=self._buf("ce_scratch", (3 * N,)))
-            else:
-                ops.softmax_ce(logits, target.contiguous(), loss, dlogits=dlogits, counts=self.hit_counts(), accumulate_counts=True,
-                               scratch=self._buf("ce_scratch", (3 * N,)))
-                self._seen += N
-        elif target.is_floating_point() and target.shape == (N, K):
-            ops.soft_ce(logits, target.float().contiguous(), loss, dlogits=dlogits, scratch=self._buf("ce_scratch", (3 * N,)))
-        else:
-            raise ValueError(f"target must be int64 labels of shape ({N},) or dense float targets of shape ({N}, {K})")
-        return loss.reshape(()), logits, eng, feat, dlogits
+        scratch = self._buf("ce_scratch", (3 * N,))
+        smoothing = float(self.smoothing) if ft and hard and self.training else 0.0
+        if hard and smoothing == 0.0:
+            ops.softmax_ce(logits, target.contiguous(), loss, dlogits=dlogits, counts=self.hit_counts(), accumulate_counts=True, scratch=scratch)
+            self._seen += N
+        else:   # LabelSmoothingCrossEntropy(s) = soft-target cross-entropy on the smoothed one-hot rows
+            dense = (ops.mixup_target(target.contiguous(), self._buf("dense_target", (N, K)), lam=1.0, smoothing=smoothing) if hard
+                     else target.float().contiguous())
+            ops.soft_ce(logits, dense, loss, dlogits=dlogits, scratch=scratch)
+        return loss.reshape(()), logits, fbn, dlogits
 
     def _finetune_backward(self, eng, gen, feat, dlogits, loss, gscale):
         from csmae_hip import ops
@@ -329,19 +307,12 @@ class VisionTransformer(nn.Module):
             anchor = self.__dict__.get("_anchor")
             if anchor is None or anchor.device != x.device:
                 anchor = self.__dict__["_anchor"] = torch.zeros((), device=x.device, requires_grad=True)
-        if self._finetune and target is not None:
-            if grad:
-                return _FinetuneFn.apply(self, x, target, anchor)
-            with torch.no_grad():
-                loss, logits, _, _, _ = self._finetune_pass(x, target, want_grad=False)
-            return loss, logits
-        if grad:
-            if any(not n.startswith("head.") for n in trainable):
+            if not self._finetune and any(not n.startswith("head.") for n in trainable):
                 raise NotImplementedError("only the head is trainable on the MI355X path (linear probing): freeze the trunk, e.g. with probe_mode(), or "
                                           f"train all of it with finetune_mode(); got requires_grad on {[n for n in trainable if not n.startswith('head.')][:3]} ...")
-            return _ProbeFn.apply(self, x, target, anchor)
+            return _HeadFn.apply(self, x, target, anchor)
         with torch.no_grad():
-            loss, logits, _, _ = self._head_pass(x, target, want_grad=False)
+            loss, logits, _, _ = self._pass(x, target, want_grad=False)
         return logits if target is None else (loss, logits)
 
 

@@ -323,7 +323,7 @@ int csmae_cast_f32_to_bf16(long long n, const float* src, void* dst, void* strea
 int csmae_cast_bf16_to_f32(long long n, const void* src, float* dst, void* stream);
 int csmae_colsum(int dtype, long long M, int N, const void* x, long long ld, float* out, void* stream);
 
-/* ---- linear probing of the frozen encoder (main_linprobe.py:515-525; added within ABI version 7, csrc/linprobe.hip).  All fp32 except the
+/* ---- linear probing of the frozen encoder (main_linprobe.py:515-525; added within ABI version 7, csrc/classify.hip).  All fp32 except the
  * token stream x of the pooling kernel. */
 /* models_vit.py:53-58 behind the last block: global_pool = 1: mean over tokens 1 .. T-1, then LayerNorm (fc_norm); 0: LayerNorm of token 0 (norm).
  * x [N, T, D] fp32 or bf16 (16-byte aligned, D % 4 == 0, D <= 4096), feat [N, D] fp32.  global_pool with T = 1 is refused. */
@@ -349,7 +349,7 @@ int csmae_softmax_ce(long long N, int K, const float* logits, const long long* l
 int csmae_lars_step(int ntensors, const long long* table, float lr, float weight_decay, float momentum, float trust, float* norms, const float* gate,
                     void* stream);
 
-/* ---- end-to-end fine-tuning (main_finetune.py, engine_finetune.py; added within ABI version 7, csrc/finetune.hip).  No atomics: two runs give the
+/* ---- end-to-end fine-tuning (main_finetune.py, engine_finetune.py; added within ABI version 7, csrc/classify.hip).  No atomics: two runs give the
  * same bits. */
 /* Reverse of csmae_probe_pool_fwd: recomputes the pooled row and its LayerNorm statistics from x [N, T, D] (fp32 or bf16), applies the LayerNorm
  * backward to dfeat [N, D] and writes the WHOLE gradient dres [N, T, D] (the dtype of x): global_pool = 1: rows 1 .. T-1 get dpooled / (T - 1), row

@@ -1,6 +1,8 @@
-"""Shared helpers of the fine-tuning tests: the micro ViT and its oracle features (as in test_linprobe_gpu.py), torch restatements of the
-fine-tune criteria and of the whole fine-tune loss (differentiable, on the CPU), and timm 0.4.12's batch-mode Mixup restated for the CPU
-test.  Restatements that a kernel is compared against alone run in float64."""
+"""Shared helpers of the linear-probing and fine-tuning tests (test_linprobe_gpu.py, test_finetune_gpu.py, test_mixup_cpu.py): the bars, the
+NaN-guarded output buffers and the elementwise comparison, the micro ViT with its oracle features and its pre-training checkpoint, torch
+restatements of the fine-tune criteria and of the whole fine-tune loss (differentiable, on the CPU), and timm 0.4.12's batch-mode Mixup
+restated for the CPU test.  Restatements that a kernel is compared against alone run in float64."""
+import argparse
 import os
 
 import numpy as np
@@ -12,7 +14,7 @@ G = os.path.join(ROOT, "tests", "golden")
 MICRO = dict(dim_model=128, encoder_num_layers=2, encoder_num_heads=2, decoder_embed_dim=64, decoder_num_layers=2, decoder_num_heads=2)
 VIT_MICRO = dict(img_size=64, patch_size=16, embed_dim=128, depth=2, num_heads=2)
 LOSS_RTOL = 1e-4
-VAL = (2e-5, 1e-6)    # rtol, atol of an fp32 kernel's values (test_linprobe_gpu.py)
+VAL = (2e-5, 1e-6)    # rtol, atol of an fp32 kernel's values
 GRAD = (1e-4, 1e-7)   # ... of its gradients
 
 
@@ -20,9 +22,49 @@ def rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
+def assert_close(actual, expected, rtol, atol, what=""):
+    a, e = actual.detach().double().cpu(), expected.detach().double().cpu()
+    assert a.shape == e.shape, (what, a.shape, e.shape)
+    err = (a - e).abs()
+    tol = atol + rtol * e.abs()
+    print(f"{what}: max|err| {float(err.max()):.3e} (ref absmax {float(e.abs().max()):.3e}), worst err/tol {float((err / tol).max()):.3f}")
+    assert bool((err <= tol).all()), f"{what}: max|err|={float(err.max()):.3e}, bad={int((err > tol).sum())}/{err.numel()}"
+
+
+def guarded(rows, cols, dtype=torch.float32):
+    """[rows, cols] view inside a NaN-filled buffer with one guard row on each side."""
+    big = torch.full((rows + 2, cols), float("nan"), device="cuda", dtype=dtype)
+    return big, big[1:rows + 1]
+
+
+def guards_intact(big):
+    return bool(torch.isnan(big[0]).all()) and bool(torch.isnan(big[-1]).all())
+
+
+def _ce_case(N, K, seed):
+    g = torch.Generator().manual_seed(seed)
+    logits = torch.randn(N, K, generator=g) * 3
+    logits[0] = torch.linspace(-80, 80, K)[torch.randperm(K, generator=g)]   # an unstable softmax overflows on this row (exp(80) ~ 5e34, squared sums beyond fp32)
+    labels = torch.randint(0, K, (N,), generator=g)
+    labels[0] = int(logits[0].argmin())
+    return logits, labels
+
+
 def micro_sd():
     d = np.load(os.path.join(G, "model_micro.npz"), allow_pickle=False)
     return {k[3:]: torch.from_numpy(np.asarray(d[k])) for k in d.files if k.startswith("sd_")}
+
+
+def write_pretrain_checkpoint(out):
+    """A micro MAE_ViT_MsLdCeCd checkpoint written by misc.save_model into the directory `out` -> its path."""
+    import models_mae
+    import util.misc as misc
+    m = models_mae.MAE_ViT_MsLdCeCd(**MICRO, input_size=64, patch_size="16", predictor_hidden_size=128)
+    sd = micro_sd()
+    m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()}, strict=True)
+    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=0.1)
+    misc.save_model(args=argparse.Namespace(output_dir=str(out)), epoch=0, model=m, model_without_ddp=m, optimizer=opt, loss_scaler=None)
+    return str(out / "checkpoint-0.pth")
 
 
 def oracle_tokens(sd, imgs, heads=2, p=16):

@@ -1,15 +1,14 @@
-"""End-to-end fine-tuning on the MI355X: the kernels of csrc/finetune.hip against torch in float64 on the CPU (outputs in NaN-guarded
+"""End-to-end fine-tuning on the MI355X: the fine-tune kernels of csrc/classify.hip against torch in float64 on the CPU (outputs in NaN-guarded
 buffers), three fine-tune steps of the micro ViT against the CPU restatement stepped with torch.optim.AdamW, gradient accumulation,
 reproducibility, and the command line.
 
-Bars: VAL / GRAD of test_linprobe_gpu.py for the fp32 kernels (fp32 round-off of a length-D / length-K reduction; the absolute floor of GRAD,
+Bars: VAL / GRAD of finetune_ref.py for the fp32 kernels (fp32 round-off of a length-D / length-K reduction; the absolute floor of GRAD,
 1e-7, is meant for gradients of a mean loss — the upstream gradients fed to the kernels here are of that size, 0.1 and below).  A bf16 output
 is one bf16 rounding away from the fp32 result: |bf16(v) - ref| <= 2^-8 |v| + |v - ref| (half an ulp of 8 significant bits), so its bound is
 2^-8 |ref| on top of GRAD.  The
 end-to-end bars are the ones the issue names: rtol 2e-3 / atol 2e-4 x scale of test_micro_variants_fp32_vs_reference_and_oracle for fp32
 gradients and parameters, LOSS_RTOL for fp32 losses; cosine >= 0.98 per tensor and the bf16 loss bar of
 test_full_size_vitb_224_n128_vs_reference for the bf16 engine."""
-import argparse
 import os
 import subprocess
 import sys
@@ -20,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 import finetune_ref as R
-from finetune_ref import GRAD, LOSS_RTOL, VAL, VIT_MICRO, rnd
+from finetune_ref import GRAD, LOSS_RTOL, VAL, VIT_MICRO, _ce_case, assert_close, guarded, guards_intact, rnd, write_pretrain_checkpoint
 
 pytestmark = pytest.mark.gpu
 ROOT = R.ROOT
@@ -35,25 +34,6 @@ def ops():
     from csmae_hip import ops as o
     csmae_hip.load()
     return o
-
-
-def assert_close(actual, expected, rtol, atol, what=""):
-    a, e = actual.detach().double().cpu(), expected.detach().double().cpu()
-    assert a.shape == e.shape, (what, a.shape, e.shape)
-    err = (a - e).abs()
-    tol = atol + rtol * e.abs()
-    print(f"{what}: max|err| {float(err.max()):.3e} (ref absmax {float(e.abs().max()):.3e}), worst err/tol {float((err / tol).max()):.3f}")
-    assert bool((err <= tol).all()), f"{what}: max|err|={float(err.max()):.3e}, bad={int((err > tol).sum())}/{err.numel()}"
-
-
-def guarded(rows, cols, dtype=torch.float32):
-    """[rows, cols] view inside a NaN-filled buffer with one guard row on each side."""
-    big = torch.full((rows + 2, cols), float("nan"), device="cuda", dtype=dtype)
-    return big, big[1:rows + 1]
-
-
-def guards_intact(big):
-    return bool(torch.isnan(big[0]).all()) and bool(torch.isnan(big[-1]).all())
 
 
 # ------------------------------------------------------------------------------------------------ pooling + final norm, backward
@@ -99,15 +79,6 @@ def test_probe_pool_bwd_refuses_a_mean_over_nothing_before_any_launch(ops):
 
 
 # ------------------------------------------------------------------------------------------------ targets, soft cross-entropy, classifier dX
-def _ce_case(N, K, seed):
-    g = torch.Generator().manual_seed(seed)
-    logits = torch.randn(N, K, generator=g) * 3
-    logits[0] = torch.linspace(-80, 80, K)[torch.randperm(K, generator=g)]   # an unstable softmax overflows on this row
-    labels = torch.randint(0, K, (N,), generator=g)
-    labels[0] = int(logits[0].argmin())
-    return logits, labels
-
-
 @pytest.mark.parametrize("N", [1, 3, 128])
 @pytest.mark.parametrize("K", [2, 5, 62, 1000])
 def test_mixup_target_soft_ce_and_head_dx_vs_fp64(ops, K, N):
@@ -415,16 +386,7 @@ def test_accumulation_reproducibility_and_generation_check(ops):
 # ------------------------------------------------------------------------------------------------ command line
 @pytest.fixture(scope="module")
 def pretrain_checkpoint(tmp_path_factory):
-    """A micro MAE_ViT_MsLdCeCd checkpoint written by misc.save_model (the recipe of test_linprobe_gpu.py)."""
-    import models_mae
-    import util.misc as misc
-    m = models_mae.MAE_ViT_MsLdCeCd(**R.MICRO, input_size=64, patch_size="16", predictor_hidden_size=128)
-    sd = R.micro_sd()
-    m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()}, strict=True)
-    out = tmp_path_factory.mktemp("pretrain")
-    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=0.1)
-    misc.save_model(args=argparse.Namespace(output_dir=str(out)), epoch=0, model=m, model_without_ddp=m, optimizer=opt, loss_scaler=None)
-    return str(out / "checkpoint-0.pth")
+    return write_pretrain_checkpoint(tmp_path_factory.mktemp("pretrain"))
 
 
 def test_cli_synthetic_epoch_checkpoint_resume_and_eval(ops, pretrain_checkpoint, tmp_path):

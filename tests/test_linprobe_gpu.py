@@ -1,11 +1,10 @@
-"""Linear probing on the MI355X: the kernels of csrc/linprobe.hip against torch in float64 on the CPU, the ViT trunk + pooling against
+"""Linear probing on the MI355X: the probe's kernels of csrc/classify.hip against torch in float64 on the CPU, the ViT trunk + pooling against
 the CPU oracle's pieces, LARS against the reference's own optimizer (tests/golden/lars.npz), and three probe steps end to end.
 
 Bars: the fp32 kernels are held to the elementwise bars the fp32 loss kernels have in tests/test_ops_gpu.py (values rtol 2e-5 / atol 1e-6,
 gradients rtol 1e-4 / atol 1e-7: fp32 round-off of a length-D or length-K reduction); trunk features to the latent bar of
 test_standalone_encoder_decoder_loss_match_oracle (atol 2e-4, rtol 1e-4) in fp32 and to test_micro_bf16_mfma_path_tracks_fp32's bar for
 tensors (cosine > 0.98) in bf16; losses to LOSS_RTOL."""
-import argparse
 import os
 import subprocess
 import sys
@@ -15,14 +14,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from finetune_ref import G, GRAD, LOSS_RTOL, ROOT, VAL, VIT_MICRO, _ce_case, assert_close, guarded, guards_intact, micro_sd, oracle_features, rnd, write_pretrain_checkpoint
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "tests", "golden")
-MICRO = dict(dim_model=128, encoder_num_layers=2, encoder_num_heads=2, decoder_embed_dim=64, decoder_num_layers=2, decoder_num_heads=2)
-VIT_MICRO = dict(img_size=64, patch_size=16, embed_dim=128, depth=2, num_heads=2)
-LOSS_RTOL = 1e-4
-VAL = (2e-5, 1e-6)    # rtol, atol of an fp32 kernel's values
-GRAD = (1e-4, 1e-7)   # ... of its gradients
 
 
 @pytest.fixture(scope="module")
@@ -33,29 +27,6 @@ def ops():
     from csmae_hip import ops as o
     csmae_hip.load()
     return o
-
-
-def assert_close(actual, expected, rtol, atol, what=""):
-    a, e = actual.detach().double().cpu(), expected.detach().double().cpu()
-    assert a.shape == e.shape, (what, a.shape, e.shape)
-    err = (a - e).abs()
-    tol = atol + rtol * e.abs()
-    print(f"{what}: max|err| {float(err.max()):.3e} (ref absmax {float(e.abs().max()):.3e}), worst err/tol {float((err / tol).max()):.3f}")
-    assert bool((err <= tol).all()), f"{what}: max|err|={float(err.max()):.3e}, bad={int((err > tol).sum())}/{err.numel()}"
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
-
-
-def guarded(rows, cols):
-    """[rows, cols] view inside a NaN-filled buffer with one guard row on each side."""
-    big = torch.full((rows + 2, cols), float("nan"), device="cuda")
-    return big, big[1:rows + 1]
-
-
-def guards_intact(big):
-    return bool(torch.isnan(big[0]).all()) and bool(torch.isnan(big[-1]).all())
 
 
 # ------------------------------------------------------------------------------------------------ pooling + final norm
@@ -115,15 +86,6 @@ def test_bn1d_refuses_one_sample_in_training_before_any_launch(ops):
 
 
 # ------------------------------------------------------------------------------------------------ classifier + cross-entropy
-def _ce_case(N, K, seed):
-    g = torch.Generator().manual_seed(seed)
-    logits = torch.randn(N, K, generator=g) * 3
-    logits[0] = torch.linspace(-80, 80, K)[torch.randperm(K, generator=g)]   # an unstable softmax overflows on this row (exp(80) ~ 5e34, squared sums beyond fp32)
-    labels = torch.randint(0, K, (N,), generator=g)
-    labels[0] = int(logits[0].argmin())
-    return logits, labels
-
-
 @pytest.mark.parametrize("N", [1, 3, 128])
 @pytest.mark.parametrize("K", [2, 5, 62, 1000])
 def test_head_linear_and_softmax_ce_vs_torch_fp64(ops, K, N):
@@ -219,29 +181,6 @@ def test_lars_matches_the_reference_after_every_step(ops):
 
 
 # ------------------------------------------------------------------------------------------------ trunk + pooling, end to end
-def T_(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def micro_sd():
-    d = np.load(os.path.join(G, "model_micro.npz"), allow_pickle=False)
-    return {k[3:]: T_(d[k]) for k in d.files if k.startswith("sd_")}
-
-
-def oracle_features(sd, imgs, global_pool, norm_w, norm_b, heads=2, p=16):
-    """The reference's forward_features (models_vit.py:39-60) from the oracle's pieces, on timm-named weights."""
-    import csmae_oracle as O
-    x = F.conv2d(imgs, sd["patch_embed.proj.weight"], sd["patch_embed.proj.bias"], stride=p).flatten(2).transpose(1, 2)
-    D = x.shape[-1]
-    pos = torch.from_numpy(O.sincos_2d(D, int(x.shape[1] ** 0.5))).float().unsqueeze(0)
-    x = torch.cat([sd["cls_token"].expand(x.shape[0], -1, -1), x], dim=1) + pos
-    i = 0
-    while f"blocks.{i}.norm1.weight" in sd:
-        x = O.vit_block(x, sd, f"blocks.{i}.", heads)
-        i += 1
-    return F.layer_norm(x[:, 1:].mean(1) if global_pool else x[:, 0], (D,), norm_w, norm_b, 1e-6)
-
-
 @pytest.fixture(scope="module")
 def trunk():
     """Micro weights under timm's names, the images, and the oracle's features for both pooling modes (computed once)."""
@@ -301,16 +240,7 @@ def lars_rule(params, mus, lr, wd, momentum=0.9, trust=0.001):
 
 @pytest.fixture(scope="module")
 def pretrain_checkpoint(tmp_path_factory):
-    """A micro MAE_ViT_MsLdCeCd checkpoint written by misc.save_model."""
-    import models_mae
-    import util.misc as misc
-    m = models_mae.MAE_ViT_MsLdCeCd(**MICRO, input_size=64, patch_size="16", predictor_hidden_size=128)
-    sd = micro_sd()
-    m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()}, strict=True)
-    out = tmp_path_factory.mktemp("pretrain")
-    opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=0.1)
-    misc.save_model(args=argparse.Namespace(output_dir=str(out)), epoch=0, model=m, model_without_ddp=m, optimizer=opt, loss_scaler=None)
-    return str(out / "checkpoint-0.pth")
+    return write_pretrain_checkpoint(tmp_path_factory.mktemp("pretrain"))
 
 
 @pytest.mark.parametrize("global_pool", [True, False])
