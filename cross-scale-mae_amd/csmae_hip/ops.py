@@ -775,4 +775,42 @@ def pos_embed_grad(dres, dpos, accumulate=False, st=None):
     check(load().csmae_pos_embed_grad(dt(dres), N, T, D, _p(dres), _p(dpos), int(bool(accumulate)), st if st is not None else stream()), "csmae_pos_embed_grad")
 
 
+# ---- k-NN evaluation (csrc/knn.hip)
+def l2_normalize(src, dst, eps=1e-12, st=None):
+    """dst [rows, D] (contiguous, fp32 or bf16) = src[r] / max(||src[r]||, eps); src fp32 [rows, D], rows may be strided."""
+    rows, D = src.shape
+    assert src.dtype == torch.float32 and src.stride(1) == 1 and dst.shape == (rows, D) and dst.is_contiguous()
+    check(load().csmae_l2_normalize(dt(src), dt(dst), rows, D, _p(src), src.stride(0), float(eps), _p(dst), st if st is not None else stream()),
+          "csmae_l2_normalize")
+    return dst
+
+
+def knn_select(sim, val, idx, base=0, Bc=None, st=None):
+    """Merge the similarity tile sim[:, :Bc] (fp32, rows may be strided; bank rows base .. base+Bc-1) into the best-k lists val / idx [Q, k]
+    (fp32 / int32, contiguous; a fresh search starts from (-inf, -1)).  k outside [1, 64] is refused."""
+    Q, k = val.shape
+    Bc = sim.shape[1] if Bc is None else int(Bc)
+    assert sim.dtype == torch.float32 and sim.shape[0] == Q and sim.stride(1) == 1 and 0 < Bc <= sim.shape[1]
+    assert val.dtype == torch.float32 and idx.dtype == torch.int32 and idx.shape == val.shape and val.is_contiguous() and idx.is_contiguous()
+    if _timer is not None:
+        _timer.begin()
+    check(load().csmae_knn_select(Q, Bc, k, _p(sim), sim.stride(0), int(base), _p(val), _p(idx), st if st is not None else stream()), "csmae_knn_select")
+    if _timer is not None:
+        _timer.end("knn_select", 4.0 * Q * Bc)   # work: the bytes of the tile
+
+
+def knn_vote(val, idx, bank_labels, num_classes, T, top5, votes=None, counts=None, query_labels=None, accumulate_counts=False, st=None):
+    """votes [Q, K] (optional) = the exp(val / T)-weighted votes of the neighbours' labels, top5 [Q, 5] int32 the best classes (ties to the lower
+    id, -1 behind the K-th); with query_labels (int64) counts [2] (+)= top-1 / top-5 hits."""
+    Q, k = val.shape
+    K = int(num_classes)
+    assert val.dtype == torch.float32 and idx.dtype == torch.int32 and idx.shape == val.shape and val.is_contiguous() and idx.is_contiguous()
+    assert bank_labels.dtype == torch.int64 and bank_labels.is_contiguous() and top5.dtype == torch.int32 and top5.shape == (Q, 5) and top5.is_contiguous()
+    assert votes is None or votes.shape == (Q, K)
+    assert query_labels is None or (query_labels.dtype == torch.int64 and query_labels.numel() == Q and query_labels.is_contiguous() and counts is not None)
+    _f32c(votes, counts)
+    check(load().csmae_knn_vote(Q, k, K, _p(val), _p(idx), _p(bank_labels), 1.0 / float(T), _p(votes), _p(top5), _p(counts), _p(query_labels),
+                                int(bool(accumulate_counts)), st if st is not None else stream()), "csmae_knn_vote")
+
+
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -373,6 +373,26 @@ int csmae_mixup_cutmix(int cutmix, long long N, int C, int H, int W, const float
 /* dpos [T, D] (+)= sum_n dres[n] for dres [N, T, D] fp32 or bf16, fp32 accumulation in sample order */
 int csmae_pos_embed_grad(int dtype, long long N, int T, int D, const void* dres, float* dpos, int accumulate, void* stream);
 
+/* ---- k-NN evaluation of the frozen encoder (main_knn.py, csmae_hip/knn.py; added within ABI version 7, csrc/knn.hip).  The similarities themselves
+ * come from csmae_gemm; these are the steps around it.  One wave per row; no atomics: two runs give the same bits. */
+/* dst [rows, D] (dense; out_dtype fp32 or bf16) = src[r] / max(||src[r]||_2, eps), src fp32 with leading dimension ld >= D, the squares summed in
+ * fp32.  Any D. */
+int csmae_l2_normalize(int in_dtype, int out_dtype, long long rows, int D, const void* src, long long ld, float eps, void* dst, void* stream);
+/* Merge one similarity tile into the running best-k lists.  sim: fp32 [Q, Bc] with leading dimension ld >= Bc (columns Bc .. ld-1 are never read),
+ * the similarities of Q queries to bank rows base .. base+Bc-1.  val [Q, k] fp32 / idx [Q, k] int32: each query's list, read and rewritten, ordered
+ * by (similarity descending, bank index ascending); unused slots are (-inf, -1), and a search starts from lists filled with exactly that.  Once
+ * tiles covering the bank have been merged — in any chunking and any order — the lists equal a stable descending sort of the whole similarity row cut
+ * at k, bit for bit.  1 <= k <= 64 (one lane of a wave per entry): anything else is refused before a launch.  Rows that are 16-byte aligned (sim
+ * aligned, ld % 4 == 0) are read as float4. */
+int csmae_knn_select(long long Q, int Bc, int k, const float* sim, long long ld, long long base, float* val, int* idx, void* stream);
+/* The weighted vote of DINO's knn_classifier over lists as csmae_knn_select leaves them: votes [Q, K] (nullable) [q, c] = sum over j with idx[q, j] >= 0
+ * and bank_labels[idx[q, j]] == c of exp(val[q, j] * inv_T), added in list order (bank_labels int64; one outside [0, K) votes for nothing).
+ * top5 [Q, 5] int32 = the five classes with the largest votes, descending, ties to the lower class id, -1 behind the K-th when K < 5.  With
+ * query_labels (int64, nullable) counts [2] (+)= the queries whose label is top5[0] / among top5, as csmae_softmax_ce's counters (accumulate_counts);
+ * without them counts is left alone.  1 <= k <= 64, 1 <= K <= 2048. */
+int csmae_knn_vote(long long Q, int k, int K, const float* val, const int* idx, const long long* bank_labels, float inv_T, float* votes, int* top5,
+                   float* counts, const long long* query_labels, int accumulate_counts, void* stream);
+
 
 /* ---- a stream confined to a subset of the compute units (ABI version 5).  The reference overlaps DDP's bucket all-reduces and autograd's
  * weight-gradient work with the main chain on CUDA streams that share every SM (main_pretrain.py:417-421); on MI355X a GEMM workgroup owns a
