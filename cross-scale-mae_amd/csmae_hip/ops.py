@@ -813,4 +813,36 @@ def knn_vote(val, idx, bank_labels, num_classes, T, top5, votes=None, counts=Non
                                 int(bool(accumulate_counts)), st if st is not None else stream()), "csmae_knn_vote")
 
 
+# ---- per-image reconstruction scores (csrc/recon_eval.hip)
+def recon_eval_workspace_floats(N, C, S):
+    n = ctypes.c_longlong(0)
+    check(load().csmae_recon_eval_workspace_floats(N, C, S, ctypes.byref(n)), "csmae_recon_eval_workspace_floats")
+    return n.value
+
+
+def recon_eval(img, pred, mean, std, p, out=None, st=None, ws=None):
+    """out [N, 4] fp32 = per image {sum (X - Y)^2, sum |X - Y|, ssim(X, Y), 0} with X = img * std + mean and Y = the un-patchified pred * std + mean.
+    img: fp32 [N, C, S, S] contiguous.  pred: fp32 or bf16 [N, L, p*p*C], or any view of that shape whose last dimension is dense (wider rows,
+    a cls row in front of each image's rows cut off by slicing): its strides are what the kernel walks.  mean, std: fp32 [C] on the device.
+    ws: recon_eval_workspace_floats(N, C, S) fp32 (allocated here when None).  The library refuses S < 11, S % p != 0 and any other dtype of pred before it launches anything."""
+    N, C, S, S2 = img.shape
+    p = int(p)
+    assert img.dtype == torch.float32 and img.is_contiguous() and S == S2 and p > 0
+    assert pred.dim() == 3 and pred.shape == (N, (S // p) ** 2, p * p * C) and pred.stride(2) == 1, (tuple(pred.shape), pred.stride(), S, p, C)
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == C and std.numel() == C and mean.is_contiguous() and std.is_contiguous()
+    if out is None:
+        out = torch.empty(N, 4, device=img.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape == (N, 4) and out.is_contiguous()
+    floats = recon_eval_workspace_floats(N, C, S)
+    part = ws if ws is not None else torch.empty(floats, device=img.device, dtype=torch.float32)
+    assert part.dtype == torch.float32 and part.is_contiguous() and part.numel() >= floats
+    if _timer is not None:
+        _timer.begin()
+    check(load().csmae_recon_eval(_DT.get(pred.dtype, -1), N, C, S, p, _p(img), _p(pred), pred.stride(1), pred.stride(0), _p(mean), _p(std), _p(part), _p(out),
+                                  st if st is not None else stream()), "csmae_recon_eval")
+    if _timer is not None:
+        _timer.end("recon_eval", (4.0 + pred.element_size()) * N * C * S * S)   # work: the bytes of both operands
+    return out
+
+
 __all__ = [n for n in dir() if not n.startswith("_")]

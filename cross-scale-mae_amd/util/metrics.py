@@ -4,7 +4,10 @@ name in mse | mae | l1 | l2 | ssim | ms_ssim (aliases ssd -> l2, sad -> l1), ret
 The four element-wise metrics are one-line reductions on whatever device the tensors live on, as in the reference (it calls
 them on CPU copies of single images).  `ssim` / `ms_ssim` are the gaussian-window structural similarity of pytorch-msssim 0.2.1
 with `data_range=1, size_average=True` (util/metrics.py:5-10,41-46): they run on the MI355X through the same HIP kernels as the
-ssim loss family (`csmae_ssim_fwd` with flags 1|2: operands as they are, signed score) — there is no CPU implementation here."""
+ssim loss family (`csmae_ssim_fwd` with flags 1|2: operands as they are, signed score) — there is no CPU implementation here.
+
+`batch_metrics(img, pred, p, names)` is the batched route of util/viz.py run_eval: ONE score PER IMAGE of a batch, straight from the normalised
+input and the model's patch rows (`csmae_recon_eval`: no planes in memory, no host sync), as fp32 tensors on the device."""
 import torch
 
 
@@ -59,6 +62,51 @@ def calc_metric(x, y, metric_name):
     name = metric_name.lower()
     name = {"ssd": "l2", "sad": "l1"}.get(name, name)
     return METRICS_DICT[name]["lambda"](x, y)
+
+
+BATCH_METRICS = ("mse", "mae", "l1", "l2", "ssim")
+
+
+def _channel_stats(v, C, dev):
+    """Per-channel statistics as the fp32 [C] device tensor the kernel reads (a tensor that already is one is used as it is: no copy, no sync)."""
+    if torch.is_tensor(v) and v.device == dev and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == C:
+        return v
+    t = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+    if t.numel() != C:
+        raise ValueError(f"{t.numel()} channel statistics for images of {C} channels")
+    return t.to(dev).contiguous()
+
+
+def batch_metrics(img, pred, p, names, mean=None, std=None):
+    """Per-image scores of a batched forward: img [N, C, S, S] normalised input, pred [N, L, p*p*C] the model's patch rows (fp32 or bf16; any
+    view with a dense last dimension), both on the GPU.  With X = img * std + mean and Y = unpatchify(pred) * std + mean (mean / std default to
+    util.viz.image_mean / image_std), -> {name: fp32 [N] on the device} for the names mse | mae | l1 | l2 | ssim (aliases ssd -> l2, sad -> l1, keyed as
+    asked); each value is what `calc_metric(X[n], Y[n], name)` scores for that one image.  One `csmae_recon_eval` launch pair, no host sync.
+    ms_ssim is not computed per image: `calc_metric` is the single-batch route for it."""
+    from csmae_hip import ops
+    names = [names] if isinstance(names, str) else list(names)
+    canon = [{"ssd": "l2", "sad": "l1"}.get(n.lower(), n.lower()) for n in names]
+    for n, c in zip(names, canon):
+        if c == "ms_ssim":
+            raise ValueError("batch_metrics does not compute ms_ssim per image: calc_metric(x, y, 'ms_ssim') is the single-batch route")
+        if c not in BATCH_METRICS:
+            raise ValueError(f"unknown metric {n!r}: batch_metrics knows {', '.join(BATCH_METRICS)} and the aliases ssd, sad")
+    if not (torch.is_tensor(img) and torch.is_tensor(pred) and img.is_cuda and pred.is_cuda) or not torch.cuda.is_available():
+        raise RuntimeError("ssim / ms_ssim run on the MI355X only (no CPU fallback)")
+    if img.dim() != 4 or img.shape[2] != img.shape[3]:
+        raise ValueError(f"batch_metrics needs a batch of square images [N, C, S, S], got {tuple(img.shape)}")
+    if mean is None or std is None:
+        from util.viz import image_mean, image_std
+        mean, std = image_mean if mean is None else mean, image_std if std is None else std
+    N, C, S, _ = img.shape
+    img = img.float().contiguous()
+    rows = ops.recon_eval(img, pred, _channel_stats(mean, C, img.device), _channel_stats(std, C, img.device), p)
+    count = float(C * S * S)
+    col = {"l2": rows[:, 0], "l1": rows[:, 1], "ssim": rows[:, 2]}
+    out = {}
+    for n, c in zip(names, canon):
+        out[n] = rows[:, 0] / count if c == "mse" else rows[:, 1] / count if c == "mae" else col[c].clone()
+    return out
 
 
 def confusion_matrix(y_true, y_pred, num_classes=None):

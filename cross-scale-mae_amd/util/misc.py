@@ -2,7 +2,9 @@
 checkpoint save/load with the reference's dict layout.  No device math lives here except the optional gradient-norm read."""
 import builtins
 import datetime
+import glob
 import os
+import random
 import time
 from collections import defaultdict, deque
 from pathlib import Path
@@ -300,3 +302,25 @@ def all_reduce_mean(x):
     t = torch.tensor(x, device=dev)
     dist.all_reduce(t)
     return (t / world_size).item()
+
+
+def seed_str_to_int(seed_str):
+    """The sum of the characters' code points (reference util/misc.py:439-444): the crop / mask seed of "image-run" strings."""
+    return sum(ord(c) for c in seed_str)
+
+
+def glob_helper(glob_pattern, max_samples=None, random_walk=False, walk_seed=None, **kwargs):
+    """Yields the files that match `glob_pattern` (recursive `**`), in glob's order and at most `max_samples` of them; with `random_walk` a
+    `random.sample` of exactly `max_samples` files instead, drawn after `random.seed(walk_seed)` when a seed is given (reference
+    util/misc.py:482-516; further keyword arguments are ignored, so one kwargs dict can serve several helpers)."""
+    assert not (random_walk and max_samples is None), "must specify max_samples if random_walk is True"
+    assert not (walk_seed is not None and not random_walk), "walkseed can only be used if random_walk is True"
+    if walk_seed is not None:
+        random.seed(walk_seed)
+    if random_walk:
+        yield from random.sample(glob.glob(glob_pattern, recursive=True), max_samples)
+        return
+    for i, path in enumerate(glob.iglob(glob_pattern, recursive=True)):
+        if max_samples is not None and i >= max_samples:
+            break
+        yield path

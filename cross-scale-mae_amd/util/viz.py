@@ -3,9 +3,21 @@ array, one masked forward of a single image -> (original, masked input, reconstr
 reconstruction pasted into the visible patches).
 
 The model forward is the HIP path (`model(x, mask_ratio=, mask_seed=)`); everything else here is host-side array handling.
-The reference's matplotlib figures (`plot_image`, `plot_reconstruction`, `add_noise`, the dataset-wide sweeps, util/viz.py:123-138,
-208-316) are plotting UI — SURVEY §2 row 19, out of scope — and are not rebuilt: `run_one_image` + `util.metrics.calc_metric` give the
-arrays and scores a figure would show."""
+The reference's matplotlib figures (`plot_image`, `plot_reconstruction`, `plot_metrics_comp`, util/viz.py:208-316,501-624) are plotting
+UI — SURVEY §2 row 19, out of scope — and are not rebuilt: `run_one_image` + `util.metrics.calc_metric` give the arrays and scores a
+figure would show.
+
+`run_eval` (reference util/viz.py:319-498) is rebuilt without its figures and as the batched GPU sweep its TODO asks for: every image of a
+folder, `num_runs_each` seeded masks (and crops) each, through several models -> `mtrs[metric][model_name]` = one score per image.  A batch
+costs one forward and one `csmae_recon_eval` (util.metrics.batch_metrics); nothing is read back before the sweep ends.  What differs from
+the reference, on purpose:
+  * images run in batches: the mask of image i, run r is still the one `run_one_image(img, model, mask_seed=seed_str_to_int(f"{i}-{r}"))`
+    draws (the batch's masking noise is built row by row from that seed), but a GEMM may round differently at another batch size;
+  * the evaluation noise (`use_noise`) is drawn ON THE DEVICE from a generator seeded with the same per-(image, run) seed — the reference
+    draws it unseeded on the host, so its noisy scores are not repeatable; this seeding is this build's own;
+  * the multi-scale variants draw ONE crop box per batch (it only enters the training loss, never the prediction that is scored);
+  * the compared original is the fp32 input the model saw, un-normalised (the reference keeps a float64 copy);
+  * the plot arguments are accepted and ignored."""
 import os
 import re
 from typing import Optional
@@ -14,7 +26,9 @@ import numpy as np
 import torch
 
 import models_mae
+from util import metrics
 from util.gpu_input import resized_crop_box
+from util.misc import glob_helper, seed_str_to_int
 
 # per-channel statistics the reference hard-codes for its plots (util/viz.py:23-24)
 image_mean = np.array([0.40558367, 0.43378946, 0.43175863])
@@ -93,3 +107,143 @@ def run_one_image(img, model, mask_seed: Optional[int] = None, **kwargs):
     xm = x * (1 - mask)
     ym = y * mask
     return x, xm, y, ym, xm + ym
+
+
+def add_noise(image, noise_type="gaussian", noise_param=0.1, generator=None):
+    """image + noise on the image's device (reference util/viz.py:123-137): gaussian = N(0, noise_param^2), poisson = Poisson(noise_param)
+    counts, s&p = Bernoulli(noise_param) ones.  `generator` (a torch.Generator of the image's device) makes the draw repeatable."""
+    if not isinstance(image, torch.Tensor):
+        image = torch.as_tensor(image)
+    if noise_type == "gaussian":
+        noise = torch.randn(image.shape, generator=generator, device=image.device, dtype=image.dtype) * noise_param
+    elif noise_type == "poisson":
+        noise = torch.poisson(torch.ones_like(image) * noise_param, generator=generator)
+    elif noise_type == "s&p":
+        noise = torch.bernoulli(torch.ones_like(image) * noise_param, generator=generator)
+    else:
+        raise ValueError(f"Invalid noise type {noise_type!r}: gaussian, poisson or s&p")
+    return image + noise
+
+
+def eval_seed(img_i, run_i):
+    """Crop seed and mask seed of run `run_i` of image `img_i` (reference util/viz.py:379,389)."""
+    return seed_str_to_int(f"{img_i}-{run_i}")
+
+
+class EvalImages(torch.utils.data.Dataset):
+    """The sweep of run_eval as a dataset: item k = run k % num_runs_each of image k // num_runs_each -> (normalised fp32 [C, S, S], its seed)."""
+
+    def __init__(self, paths, img_size, num_runs_each, random_crop=False, resample=None):
+        self.paths, self.img_size, self.runs, self.random_crop, self.resample = list(paths), img_size, num_runs_each, random_crop, resample
+
+    def __len__(self):
+        return len(self.paths) * self.runs
+
+    def __getitem__(self, k):
+        i, r = divmod(k, self.runs)
+        seed = eval_seed(i, r)
+        img = prepare_image(self.paths[i], self.img_size, random_crop=self.random_crop, crop_seed=seed, resample=self.resample)
+        return torch.from_numpy(np.ascontiguousarray(img.transpose(2, 0, 1))).float(), seed
+
+
+class SyntheticEvalImages(torch.utils.data.Dataset):
+    """`n` seeded smooth images instead of files (the driver's --dataset_type synthetic): a coarse random grid per channel, enlarged bicubically,
+    clamped to [0, 1] and normalised like prepare_image's output.  Every run of an image sees the same picture (there is nothing to crop)."""
+
+    def __init__(self, n, img_size, num_runs_each, channels=3):
+        self.n, self.img_size, self.runs, self.channels = n, img_size, num_runs_each, channels
+
+    def __len__(self):
+        return self.n * self.runs
+
+    def __getitem__(self, k):
+        i, r = divmod(k, self.runs)
+        g = torch.Generator().manual_seed(1000 + i)
+        coarse = torch.rand(1, self.channels, 6, 6, generator=g)
+        img = torch.nn.functional.interpolate(coarse, size=(self.img_size, self.img_size), mode="bicubic", align_corners=False)[0].clamp(0.0, 1.0)
+        c = np.arange(self.channels) % len(image_mean)
+        mean, std = torch.as_tensor(image_mean[c], dtype=torch.float32), torch.as_tensor(image_std[c], dtype=torch.float32)
+        return (img - mean[:, None, None]) / std[:, None, None], eval_seed(i, r)
+
+
+def mask_draws(model, seeds, device):
+    """The masking noise of a batch whose row j is image-run seed `seeds[j]`: exactly what `torch.manual_seed(seed_j); torch.rand(1, L)` gives on
+    the device, so row j's mask is the one `model(x_j, mask_ratio, mask_seed=seed_j)` draws.  -> (noise, box) as `model._run` takes them: the
+    multi-scale variants get the noise of both views (the same rows: they re-seed before each view) and one crop box, drawn under the first seed."""
+    L = model.num_patches
+    rows = []
+    for s in seeds:
+        torch.manual_seed(int(s))
+        rows.append(torch.rand(1, L, device=device))
+    noise = torch.cat(rows, dim=0)
+    if not hasattr(model, "ms_range"):
+        return noise, None
+    from models_mae.MAE_ViT_MsLd import sample_crop_box
+    torch.manual_seed(int(seeds[0]))
+    box = torch.tensor(tuple(int(v) for v in sample_crop_box(model.input_size, model.ms_range)), dtype=torch.int32)
+    return torch.cat([noise, noise], dim=0), box
+
+
+def eval_noise(imgs, seeds, use_noise):
+    """`add_noise(imgs[j], *use_noise)` under a device generator seeded with seeds[j], row by row (a row does not depend on its batch)."""
+    if use_noise is None:
+        return imgs
+    gen = torch.Generator(device=imgs.device)
+    return torch.stack([add_noise(imgs[j], use_noise[0], use_noise[1], generator=gen.manual_seed(int(s))) for j, s in enumerate(seeds)])
+
+
+@torch.no_grad()
+def eval_batch(model, imgs, seeds, names, mean=None, std=None):
+    """The inner step of run_eval: one masked forward of the batch `imgs` (on the device; row j masked under seeds[j]) and one recon_eval of the
+    returned prediction -> {name: fp32 [n] on the device}.  Nothing is read back."""
+    noise, box = mask_draws(model, seeds, imgs.device)
+    pred = model._run(imgs, getattr(model, "mask_ratio", 0.75), noise, box)[1]
+    return metrics.batch_metrics(imgs, pred, model.patch_size, names, mean, std)
+
+
+def run_eval(models, basedir, comp_metrics=None, use_noise=None, num_runs_each=5, batch_size=64, random_crop=False, max_samples=None,
+             random_walk=False, walk_seed=None, resample=None, num_workers=4, images=None, **kwargs):
+    """Scores of every `<basedir>/**/*.jpg` under each model of the dict `models`: `mtrs[metric][model_name]` = a list with one float per image, the
+    mean over `num_runs_each` runs (run r of image i: crop seed and mask seed seed_str_to_int(f"{i}-{r}")).  `comp_metrics`: a name or a list of
+    names of util.metrics.batch_metrics; None = all of METRICS_DICT but ms_ssim, as in the reference.  `use_noise`: e.g. ("gaussian", 0.25).
+    `images`: a callable img_size -> dataset of (image, seed) items in EvalImages' order, instead of the files (main_recon_eval.py's synthetic
+    images).  The reference's plot arguments (do_plot_metrics_comp, do_plot_image_comp, plot_every, title, ...) are accepted and ignored."""
+    if not isinstance(models, dict):
+        models = {"model": models}
+    if comp_metrics is not None:
+        names = [comp_metrics] if isinstance(comp_metrics, str) else list(comp_metrics)
+    else:
+        names = [m for m in metrics.METRICS_DICT if m != "ms_ssim"]   # (needs images larger than 160 px; per-image ms_ssim is not built)
+    if kwargs:
+        print(f"run_eval: no figures in this build, ignoring {sorted(kwargs)}")
+    paths = None if images is not None else list(glob_helper(f"{basedir}/**/*.jpg", max_samples=max_samples, random_walk=random_walk, walk_seed=walk_seed))
+    scores = {name: {model_name: [] for model_name in models} for name in names}
+    n_items = 0
+    for size in sorted({m.input_size for m in models.values()}):
+        group = {k: m for k, m in models.items() if m.input_size == size}
+        ds = images(size) if images is not None else EvalImages(paths, size, num_runs_each, random_crop=random_crop, resample=resample)
+        n_items = len(ds)
+        loader = torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=num_workers, pin_memory=True, drop_last=False)
+        stats = {}
+        for imgs, seeds in loader:   # (the workers decode the next batches while the GPU runs this one)
+            seeds = seeds.tolist()
+            clean = {}
+            for model_name, model in group.items():
+                dev = torch.device(model.device) if model.device is not None else next(model.parameters()).device
+                if dev not in clean:
+                    clean[dev] = eval_noise(imgs.to(dev, non_blocking=True), seeds, use_noise)
+                    if dev not in stats:
+                        C = imgs.shape[1]
+                        c = np.arange(C) % len(image_mean)
+                        stats[dev] = (torch.as_tensor(image_mean[c], dtype=torch.float32).to(dev), torch.as_tensor(image_std[c], dtype=torch.float32).to(dev))
+                got = eval_batch(model, clean[dev], seeds, names, *stats[dev])
+                for name in names:
+                    scores[name][model_name].append(got[name])
+    n_images = n_items // max(num_runs_each, 1)
+    mtrs = {name: {} for name in names}
+    for name in names:
+        for model_name in models:
+            per_run = torch.cat(scores[name][model_name]).double().cpu() if scores[name][model_name] else torch.zeros(0, dtype=torch.float64)
+            mtrs[name][model_name] = (per_run.view(n_images, num_runs_each).sum(1) / num_runs_each).tolist()
+    print(f"# Finished evaluating on: {basedir} - {n_images} images for {len(models)} models ({num_runs_each} runs each)")
+    return mtrs

@@ -393,6 +393,19 @@ int csmae_knn_select(long long Q, int Bc, int k, const float* sim, long long ld,
 int csmae_knn_vote(long long Q, int k, int K, const float* val, const int* idx, const long long* bank_labels, float inv_T, float* votes, int* top5,
                    float* counts, const long long* query_labels, int accumulate_counts, void* stream);
 
+/* ---- per-image reconstruction scores of a batch (util/metrics.py batch_metrics, util/viz.py run_eval; added within ABI version 7,
+ * csrc/recon_eval.hip).  With X = img * std + mean and Y = the un-patchified pred * std + mean (mean, std: [C] fp32 on the device):
+ *   out[n] = { sum (X - Y)^2, sum |X - Y|, ssim(X, Y), 0 }   (fp32 [N][4]; the sums run over all C S S elements of image n)
+ * ssim is pytorch-msssim 0.2.1's (11-tap gaussian, sigma 1.5, valid windows, data_range 1, signed: no relu), the mean over the C planes.
+ * img: fp32 [N, C, S, S].  pred (pred_dtype fp32 or bf16): patch row l = (y / p) (S / p) + x / p of image n starts at pred + n img_stride + l ldp
+ * and holds pixel (c, y, x) at element ((y % p) p + x % p) C + c; ldp >= p p C, elements behind a row's p p C are never read.  A cls row in
+ * front of each image's rows is skipped by the caller: pass pred + ldp and img_stride = (L + 1) ldp.  part: csmae_recon_eval_workspace_floats
+ * floats.  No plane is written to memory; two launches, no atomics; an image's four floats depend on that image alone (not on N, not on n).
+ * Refused before any launch: S < 11, S % p != 0, C < 1, a null pointer, a pred_dtype other than fp32 / bf16. */
+int csmae_recon_eval_workspace_floats(long long N, int C, int S, long long* floats /* host pointer, out */);
+int csmae_recon_eval(int pred_dtype, long long N, int C, int S, int p, const float* img, const void* pred, long long ldp, long long img_stride,
+                     const float* mean, const float* std, float* part, float* out, void* stream);
+
 
 /* ---- a stream confined to a subset of the compute units (ABI version 5).  The reference overlaps DDP's bucket all-reduces and autograd's
  * weight-gradient work with the main chain on CUDA streams that share every SM (main_pretrain.py:417-421); on MI355X a GEMM workgroup owns a
