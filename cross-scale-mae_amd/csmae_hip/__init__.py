@@ -1,5 +1,7 @@
 """ctypes binding of libcsmae_hip.so (the gfx950 C ABI declared in include/csmae.h).
 
+The constants and _SIGNATURES below restate the header by hand; tests/test_abi_cpu.py holds them to it.
+
 There is deliberately NO fallback: if the shared library is missing or a kernel launch fails, the
 product path raises.  PyTorch is used only for device memory, streams and torch.distributed.
 """
@@ -13,7 +15,8 @@ import torch  # noqa: F401  -- must come first: libcsmae_hip.so has to bind to t
 
 F32, BF16 = 0, 1
 ABI_VERSION = 7
-EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_ATOMIC = 0, 1, 2, 3, 4
+EPI_NONE, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_ATOMIC, EPI_SPLIT = 0, 1, 2, 3, 4, 5
+EPI_GELU_Q8, EPI_DGELU_Q8 = 6, 7   # GELU / DGELU with aux = gelu'(x) as one byte per element (ops picks them when aux is a uint8 tensor)
 ROUTE_F32, ROUTE_KSLAB = 7, 8   # csmae_gemm_route / csmae_gemm_ks_route codes beside the bf16 tile configurations 0..6
 ATTN_ROUTE_RESIDENT, ATTN_ROUTE_STREAM, ATTN_ROUTE_ANY, ATTN_ROUTE_F32 = 0, 1, 2, 3   # csmae_attn_route
 ATTN_STREAM_OWN, ATTN_STREAM_TILE = 128, 64   # rows a streaming-attention workgroup owns / rows of one streamed tile (csrc/attention_common.h)

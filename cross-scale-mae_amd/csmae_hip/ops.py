@@ -8,9 +8,11 @@ import ctypes
 import torch
 
 from . import BF16, EPI_ATOMIC, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_RESID, F32, LOSS_KINDS, check, load
+from . import EPI_DGELU_Q8 as _EPI_DGELU_Q8, EPI_GELU_Q8 as _EPI_GELU_Q8   # (private here: __all__ below is every public name of this module)
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 _timer = None
+_Q8 = {EPI_GELU: _EPI_GELU_Q8, EPI_DGELU: _EPI_DGELU_Q8}
 
 
 class KernelTimer:
@@ -62,6 +64,25 @@ def _p(t):
 
 def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _s(st):
+    """the `st` argument of every launcher: a raw stream handle, or None for torch's current stream"""
+    return st if st is not None else stream()
+
+
+def _begin():
+    """Start of a timed launch: `t = _begin()`, the launch, `if t: t.end(kind, work)`.  Returns the active KernelTimer (start event recorded) or None."""
+    if _timer is not None:
+        _timer.begin()
+    return _timer
+
+
+def _epi(epilogue, aux):
+    """gelu' as one byte per element: a uint8 `aux` turns the GELU / DGELU epilogue into its _Q8 code"""
+    if aux is not None and aux.dtype == torch.uint8:
+        return _Q8[epilogue]
+    return epilogue
 
 
 _masked = {}
@@ -127,15 +148,12 @@ def gemm(a, b, out, *, trans_a=False, trans_b=False, bias=None, epilogue=EPI_NON
     assert K == Kb and out.shape[0] == M and out.shape[1] == N, (a.shape, b.shape, out.shape, trans_a, trans_b)
     assert a.dtype == b.dtype and a.stride(1) == 1 and b.stride(1) == 1 and out.stride(1) == 1
     assert resid is None or resid.dtype == out.dtype, "the residual epilogue reads its addend in the output's dtype"
-    if aux is not None and aux.dtype == torch.uint8:   # gelu' as one byte per element (CSMAE_EPI_GELU_Q8 / CSMAE_EPI_DGELU_Q8)
-        epilogue = {EPI_GELU: 6, EPI_DGELU: 7}[epilogue]
-    if _timer is not None:
-        _timer.begin()
-    check(load().csmae_gemm(dt(a), int(trans_a), int(trans_b), M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0),
-                            dt(out), _p(bias), epilogue, _p(aux), aux.stride(0) if aux is not None else 0, _p(resid),
-                            resid.stride(0) if resid is not None else 0, splitk, st if st is not None else stream()), "csmae_gemm")
-    if _timer is not None:
-        _timer.end(("gemm_bf16" if a.dtype == torch.bfloat16 else "gemm_f32") + ("_T" if trans_a else "_N") + ("N" if trans_b else "T"), 2.0 * M * N * K)
+    epilogue = _epi(epilogue, aux)
+    t = _begin()
+    check(load().csmae_gemm(dt(a), int(trans_a), int(trans_b), M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), dt(out), _p(bias), epilogue,
+                            _p(aux), aux.stride(0) if aux is not None else 0, _p(resid), resid.stride(0) if resid is not None else 0, splitk, _s(st)), "csmae_gemm")
+    if t:
+        t.end(("gemm_bf16" if a.dtype == torch.bfloat16 else "gemm_f32") + ("_T" if trans_a else "_N") + ("N" if trans_b else "T"), 2.0 * M * N * K)
     return out
 
 
@@ -143,8 +161,7 @@ def gemm_route(a, b, out, *, trans_a=False, trans_b=False, epilogue=EPI_NONE, au
     """The kernel gemm() would launch with these arguments (csmae_gemm_route, no launch): a bf16 tile configuration 0..6 or ROUTE_F32."""
     K, M = (a.shape[0], a.shape[1]) if trans_a else (a.shape[1], a.shape[0])
     N = b.shape[1] if trans_b else b.shape[0]
-    if aux is not None and aux.dtype == torch.uint8:
-        epilogue = {EPI_GELU: 6, EPI_DGELU: 7}[epilogue]
+    epilogue = _epi(epilogue, aux)
     rc = load().csmae_gemm_route(dt(a), int(trans_a), int(trans_b), M, N, K, a.stride(0), b.stride(0), out.stride(0), epilogue, splitk)
     check(min(rc, 0), "csmae_gemm_route")
     return rc
@@ -154,8 +171,7 @@ def gemm_ks_route(a, bk, b_plain, out, *, epilogue=EPI_NONE, aux=None):
     """The kernel gemm_ks() would launch with these arguments (csmae_gemm_ks_route): ROUTE_KSLAB, or gemm_route() of its plain-weight fallback."""
     M, K = a.shape
     N = b_plain.shape[0]
-    if aux is not None and aux.dtype == torch.uint8:
-        epilogue = {EPI_GELU: 6, EPI_DGELU: 7}[epilogue]
+    epilogue = _epi(epilogue, aux)
     rc = load().csmae_gemm_ks_route(dt(a), M, N, K, _p(a), a.stride(0), _p(bk), N, b_plain.stride(0), _p(out), out.stride(0), epilogue)
     check(min(rc, 0), "csmae_gemm_ks_route")
     return rc
@@ -169,15 +185,12 @@ def gemm_ks(a, bk, b_plain, out, *, bias=None, epilogue=EPI_NONE, aux=None, resi
     assert b_plain.shape[1] == K and out.shape == (M, N) and a.stride(1) == 1 and out.stride(1) == 1 and b_plain.stride(1) == 1
     assert resid is None or resid.dtype == out.dtype
     assert bk.dtype == torch.bfloat16 and bk.is_contiguous() and bk.numel() >= N * K, "gemm_ks: the K-slab mirror is a flat bf16 tensor of N * K elements"
-    if aux is not None and aux.dtype == torch.uint8:
-        epilogue = {EPI_GELU: 6, EPI_DGELU: 7}[epilogue]
-    if _timer is not None:
-        _timer.begin()
-    check(load().csmae_gemm_ks(dt(a), M, N, K, _p(a), a.stride(0), _p(bk), N, _p(b_plain), b_plain.stride(0), _p(out), out.stride(0), dt(out), _p(bias),
-                               epilogue, _p(aux), aux.stride(0) if aux is not None else 0, _p(resid), resid.stride(0) if resid is not None else 0,
-                               st if st is not None else stream()), "csmae_gemm_ks")
-    if _timer is not None:
-        _timer.end(("gemm_bf16" if a.dtype == torch.bfloat16 else "gemm_f32") + "_NT", 2.0 * M * N * K)
+    epilogue = _epi(epilogue, aux)
+    t = _begin()
+    check(load().csmae_gemm_ks(dt(a), M, N, K, _p(a), a.stride(0), _p(bk), N, _p(b_plain), b_plain.stride(0), _p(out), out.stride(0), dt(out), _p(bias), epilogue,
+                               _p(aux), aux.stride(0) if aux is not None else 0, _p(resid), resid.stride(0) if resid is not None else 0, _s(st)), "csmae_gemm_ks")
+    if t:
+        t.end(("gemm_bf16" if a.dtype == torch.bfloat16 else "gemm_f32") + "_NT", 2.0 * M * N * K)
     return out
 
 
@@ -194,12 +207,11 @@ def gemm_ln_fwd(a, bk, bias, resid, x_out, gamma, beta, y, mean, rstd, eps=1e-6,
     assert a.dtype == resid.dtype == x_out.dtype == y.dtype == bk.dtype == torch.bfloat16 and bk.is_contiguous() and bk.numel() >= N * K
     assert resid.shape == x_out.shape == y.shape == (M, N) and a.stride(1) == resid.stride(1) == x_out.stride(1) == y.stride(1) == 1
     assert mean.dtype == rstd.dtype == torch.float32 and mean.numel() >= M and rstd.numel() >= M and gamma.numel() == beta.numel() == N
-    if _timer is not None:
-        _timer.begin()
+    t = _begin()
     check(load().csmae_gemm_ln_fwd(M, N, K, _p(a), a.stride(0), _p(bk), N, _p(bias), _p(resid), resid.stride(0), _p(x_out), x_out.stride(0), _p(gamma), _p(beta),
-                                   eps, _p(y), y.stride(0), _p(mean), _p(rstd), st if st is not None else stream()), "csmae_gemm_ln_fwd")
-    if _timer is not None:
-        _timer.end("gemm_bf16_NT", 2.0 * M * N * K)
+                                   eps, _p(y), y.stride(0), _p(mean), _p(rstd), _s(st)), "csmae_gemm_ln_fwd")
+    if t:
+        t.end("gemm_bf16_NT", 2.0 * M * N * K)
 
 
 def gemm_ln_bwd(dy, w, x, mean, rstd, gamma, dres_in, dx_out, partial_ws=None, st=None):
@@ -210,18 +222,17 @@ def gemm_ln_bwd(dy, w, x, mean, rstd, gamma, dres_in, dx_out, partial_ws=None, s
     assert w.shape[0] == K and x.shape == dx_out.shape == (M, N) and (dres_in is None or dres_in.shape == (M, N))
     assert dy.dtype == w.dtype == x.dtype == dx_out.dtype == torch.bfloat16 and (dres_in is None or dres_in.dtype == torch.bfloat16)
     assert dy.stride(1) == w.stride(1) == x.stride(1) == dx_out.stride(1) == 1 and mean.dtype == rstd.dtype == torch.float32
-    if _timer is not None:
-        _timer.begin()
+    t = _begin()
     check(load().csmae_gemm_ln_bwd(M, N, K, _p(dy), dy.stride(0), _p(w), w.stride(0), _p(x), x.stride(0), _p(mean), _p(rstd), _p(gamma), _p(dres_in),
                                    dres_in.stride(0) if dres_in is not None else 0, _p(dx_out), dx_out.stride(0), _p(partial_ws),
-                                   partial_ws.numel() if partial_ws is not None else 0, st if st is not None else stream()), "csmae_gemm_ln_bwd")
-    if _timer is not None:
-        _timer.end("gemm_bf16_NN", 2.0 * M * N * K)
+                                   partial_ws.numel() if partial_ws is not None else 0, _s(st)), "csmae_gemm_ln_bwd")
+    if t:
+        t.end("gemm_bf16_NN", 2.0 * M * N * K)
 
 
 def weights_kslab(desc, src, dst, max_blocks=64, st=None):
     """K-slab mirrors (csmae.h csmae_gemm_ks) of the weights in desc (int64 [count, 3] on the device: flat offset, out, in) from the bf16 mirror."""
-    check(load().csmae_weights_kslab(desc.shape[0], _p(desc), max_blocks, _p(src), _p(dst), st if st is not None else stream()), "csmae_weights_kslab")
+    check(load().csmae_weights_kslab(desc.shape[0], _p(desc), max_blocks, _p(src), _p(dst), _s(st)), "csmae_weights_kslab")
 
 
 def gemm_dw(dy, x, dw, workspace, db=None, st=None):
@@ -229,12 +240,10 @@ def gemm_dw(dy, x, dw, workspace, db=None, st=None):
     K, M = dy.shape
     N = x.shape[1]
     assert x.shape[0] == K and dw.shape == (M, N) and dw.is_contiguous() and dy.dtype == x.dtype
-    if _timer is not None:
-        _timer.begin()
-    check(load().csmae_gemm_dw(dt(dy), M, N, K, _p(dy), dy.stride(0), _p(x), x.stride(0), _p(dw), _p(db), _p(workspace), workspace.numel(),
-                               st if st is not None else stream()), "csmae_gemm_dw")
-    if _timer is not None:
-        _timer.end(("gemm_bf16" if dy.dtype == torch.bfloat16 else "gemm_f32") + "_TN", 2.0 * M * N * K)
+    t = _begin()
+    check(load().csmae_gemm_dw(dt(dy), M, N, K, _p(dy), dy.stride(0), _p(x), x.stride(0), _p(dw), _p(db), _p(workspace), workspace.numel(), _s(st)), "csmae_gemm_dw")
+    if t:
+        t.end(("gemm_bf16" if dy.dtype == torch.bfloat16 else "gemm_f32") + "_TN", 2.0 * M * N * K)
 
 
 # ---- fp8 MFMA path (BASELINE.json configs[4])
@@ -249,7 +258,7 @@ def fp8_quantize(src, dst, amax, dq, fmt=FP8_E4M3, transpose=False, amax_next=No
     transpose: dst is [cols, rows] (weight mirror for dX)."""
     rows, cols = src.shape
     assert dst.dtype == torch.uint8 and dst.shape == ((cols, rows) if transpose else (rows, cols)) and src.stride(1) == 1 and dst.stride(1) == 1
-    s = st if st is not None else stream()
+    s = _s(st)
     if amax_next is None:
         check(load().csmae_fp8_amax(dt(src), rows, cols, _p(src), src.stride(0), _p(amax), s), "csmae_fp8_amax")
     check(load().csmae_fp8_quantize(dt(src), fmt, int(transpose), rows, cols, _p(src), src.stride(0), _p(dst), dst.stride(0), _p(amax), _p(dq),
@@ -261,7 +270,7 @@ FP8_SLOTS = 64   # an amax is 64 partial maxima (see csrc/fp8.hip)
 
 def fp8_weights(desc, p, w8, w8t, amax, dq, st=None):
     """All fp8 weight mirrors in three launches: desc int64 [count, 3] = (offset in p / w8 / w8t, out, in); amax [count, 64] zeroed, dq [count]."""
-    check(load().csmae_fp8_weights(desc.shape[0], _p(desc), _p(p), _p(w8), _p(w8t), _p(amax), _p(dq), st if st is not None else stream()), "csmae_fp8_weights")
+    check(load().csmae_fp8_weights(desc.shape[0], _p(desc), _p(p), _p(w8), _p(w8t), _p(amax), _p(dq), _s(st)), "csmae_fp8_weights")
 
 
 def gemm_fp8(a8, b8, out, dq_a, dq_b, *, a_fmt=FP8_E4M3, bias=None, epilogue=EPI_NONE, aux=None, resid=None, emit=None, skip_out=False, st=None):
@@ -273,18 +282,27 @@ def gemm_fp8(a8, b8, out, dq_a, dq_b, *, a_fmt=FP8_E4M3, bias=None, epilogue=EPI
     N = b8.shape[0]
     assert a8.dtype == torch.uint8 and b8.dtype == torch.uint8 and b8.shape[1] == K and out.shape == (M, N)
     assert resid is None or resid.dtype == out.dtype
-    if aux is not None and aux.dtype == torch.uint8:
-        epilogue = {EPI_GELU: 6, EPI_DGELU: 7}[epilogue]
-    if _timer is not None:
-        _timer.begin()
+    epilogue = _epi(epilogue, aux)
+    q_out, *q_rest = _emit_args(emit)   # (csmae_gemm_fp8 takes the copy's row stride behind its pointer)
+    t = _begin()
     check(load().csmae_gemm_fp8(a_fmt, M, N, K, _p(a8), a8.stride(0), _p(b8), b8.stride(0), None if skip_out else _p(out), out.stride(0), dt(out), _p(bias), epilogue,
                                 _p(aux), aux.stride(0) if aux is not None else 0, _p(resid), resid.stride(0) if resid is not None else 0,
-                                _p(dq_a), _p(dq_b), _p(emit[0]) if emit else None, emit[0].stride(0) if emit else 0, emit[1] if emit else 0,
-                                _p(emit[2]) if emit else None, _p(emit[3]) if emit else None, _p(emit[4]) if emit else None,
-                                st if st is not None else stream()), "csmae_gemm_fp8")
-    if _timer is not None:
-        _timer.end("gemm_fp8_NT", 2.0 * M * N * K)
+                                _p(dq_a), _p(dq_b), q_out, emit[0].stride(0) if emit else 0, *q_rest, _s(st)), "csmae_gemm_fp8")
+    if t:
+        t.end("gemm_fp8_NT", 2.0 * M * N * K)
     return out
+
+
+def _dw_group_args(self, products, workspace, dy, x, dw, db):
+    """What DwGroup and DwGroup8 share: the host arrays of device pointers and sizes of a grouped weight-gradient launch, after self.K is set.
+    dy, x, dw, db: where a product tuple holds those tensors."""
+    VP, LL = ctypes.c_void_p * len(products), ctypes.c_longlong * len(products)
+    self.n, self.keep = len(products), (products, workspace)
+    self.dY, self.X, self.dW, self.dB = (VP(*[_p(q[i]) for q in products]) for i in (dy, x, dw, db))
+    self.ldy, self.ldx = LL(*[q[dy].stride(0) for q in products]), LL(*[q[x].stride(0) for q in products])
+    self.M, self.N = LL(*[q[dw].shape[0] for q in products]), LL(*[q[dw].shape[1] for q in products])
+    self.flops = sum(2.0 * q[dw].shape[0] * q[dw].shape[1] * self.K for q in products)
+    self.ws, self.ws_n = _p(workspace), workspace.numel()
 
 
 class DwGroup:
@@ -293,28 +311,18 @@ class DwGroup:
 
     def __init__(self, products, workspace):
         """products: [(dy [K, >=M], x [K, >=N], dw [M, N] fp32 contiguous, db [M] fp32 or None)] with one K."""
-        n = len(products)
         self.K = products[0][0].shape[0]
         self.dtype = dt(products[0][0])
-        self.keep = (products, workspace)
         for dy, x, dw, db in products:
             assert dy.shape[0] == self.K and x.shape[0] == self.K and dw.is_contiguous() and dy.dtype == x.dtype and dy.stride(1) == 1 and x.stride(1) == 1
-        VP, LL = ctypes.c_void_p * n, ctypes.c_longlong * n
-        self.n = n
-        self.dY, self.X = VP(*[_p(q[0]) for q in products]), VP(*[_p(q[1]) for q in products])
-        self.dW, self.dB = VP(*[_p(q[2]) for q in products]), VP(*[_p(q[3]) for q in products])
-        self.ldy, self.ldx = LL(*[q[0].stride(0) for q in products]), LL(*[q[1].stride(0) for q in products])
-        self.M, self.N = LL(*[q[2].shape[0] for q in products]), LL(*[q[2].shape[1] for q in products])
-        self.flops = sum(2.0 * q[2].shape[0] * q[2].shape[1] * self.K for q in products)
-        self.ws, self.ws_n = _p(workspace), workspace.numel()
+        _dw_group_args(self, products, workspace, 0, 1, 2, 3)
 
     def launch(self, slots=0, st=None):
-        if _timer is not None:
-            _timer.begin()
+        t = _begin()
         check(load().csmae_gemm_dw_group(self.dtype, self.n, self.K, self.dY, self.ldy, self.X, self.ldx, self.dW, self.dB, self.M, self.N, slots,
-                                         self.ws, self.ws_n, st if st is not None else stream()), "csmae_gemm_dw_group")
-        if _timer is not None:
-            _timer.end(("gemm_bf16" if self.dtype == BF16 else "gemm_f32") + "_TN", self.flops)
+                                         self.ws, self.ws_n, _s(st)), "csmae_gemm_dw_group")
+        if t:
+            t.end(("gemm_bf16" if self.dtype == BF16 else "gemm_f32") + "_TN", self.flops)
 
 
 class DwGroup8:
@@ -322,29 +330,19 @@ class DwGroup8:
     dq_x [1], dw [M, N] fp32 contiguous, db [M] fp32 or None)] over one K."""
 
     def __init__(self, products, workspace):
-        n = len(products)
         self.K = products[0][0].shape[0]
-        self.keep = (products, workspace)
         for dy, dqy, x, dqx, dw, db in products:
             assert dy.dtype == x.dtype == torch.uint8 and dy.shape[0] == x.shape[0] == self.K and dy.stride(1) == x.stride(1) == 1 and dw.is_contiguous()
             assert dqy.dtype == dqx.dtype == torch.float32 and dqy.numel() >= 1 and dqx.numel() >= 1
-        VP, LL = ctypes.c_void_p * n, ctypes.c_longlong * n
-        self.n = n
-        self.dY, self.X = VP(*[_p(q[0]) for q in products]), VP(*[_p(q[2]) for q in products])
-        self.dqy, self.dqx = VP(*[_p(q[1]) for q in products]), VP(*[_p(q[3]) for q in products])
-        self.dW, self.dB = VP(*[_p(q[4]) for q in products]), VP(*[_p(q[5]) for q in products])
-        self.ldy, self.ldx = LL(*[q[0].stride(0) for q in products]), LL(*[q[2].stride(0) for q in products])
-        self.M, self.N = LL(*[q[4].shape[0] for q in products]), LL(*[q[4].shape[1] for q in products])
-        self.flops = sum(2.0 * q[4].shape[0] * q[4].shape[1] * self.K for q in products)
-        self.ws, self.ws_n = _p(workspace), workspace.numel()
+        _dw_group_args(self, products, workspace, 0, 2, 4, 5)
+        self.dqy, self.dqx = ((ctypes.c_void_p * self.n)(*[_p(q[i]) for q in products]) for i in (1, 3))
 
     def launch(self, slots=0, st=None):
-        if _timer is not None:
-            _timer.begin()
+        t = _begin()
         check(load().csmae_gemm_dw_group_fp8(self.n, self.K, self.dY, self.ldy, self.dqy, self.X, self.ldx, self.dqx, self.dW, self.dB, self.M, self.N, slots,
-                                             self.ws, self.ws_n, st if st is not None else stream()), "csmae_gemm_dw_group_fp8")
-        if _timer is not None:
-            _timer.end("gemm_fp8_TN", self.flops)
+                                             self.ws, self.ws_n, _s(st)), "csmae_gemm_dw_group_fp8")
+        if t:
+            t.end("gemm_fp8_TN", self.flops)
 
 
 def attn_resident(dtype_code, T, hd):
@@ -370,18 +368,18 @@ def attn_stream_mode(mode=-1):
 def attn_fwd(qkv, out, lse, B, T, H, hd, emit=None, st=None):
     """emit = (q_out uint8 [B*T, H*hd], fmt, amax_prev [64], amax_next [64], dq [1]): also write `out` as fp8 bytes for attn.proj's GEMM."""
     if emit is None:
-        check(load().csmae_attn_fwd(dt(qkv), B, T, H, hd, _p(qkv), _p(out), _p(lse), st if st is not None else stream()), "csmae_attn_fwd")
+        check(load().csmae_attn_fwd(dt(qkv), B, T, H, hd, _p(qkv), _p(out), _p(lse), _s(st)), "csmae_attn_fwd")
     else:
-        check(load().csmae_attn_fwd_q(dt(qkv), B, T, H, hd, _p(qkv), _p(out), _p(lse), *_emit_args(emit), st if st is not None else stream()), "csmae_attn_fwd_q")
+        check(load().csmae_attn_fwd_q(dt(qkv), B, T, H, hd, _p(qkv), _p(out), _p(lse), *_emit_args(emit), _s(st)), "csmae_attn_fwd_q")
 
 
 def attn_bwd(qkv, out, dout, lse, dqkv, B, T, H, hd, emit=None, skip_out=False, st=None):
     """skip_out (with emit): only the fp8 copy of dqkv is written."""
     assert not skip_out or emit is not None
     if emit is None:
-        check(load().csmae_attn_bwd(dt(qkv), B, T, H, hd, _p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), st if st is not None else stream()), "csmae_attn_bwd")
+        check(load().csmae_attn_bwd(dt(qkv), B, T, H, hd, _p(qkv), _p(out), _p(dout), _p(lse), _p(dqkv), _s(st)), "csmae_attn_bwd")
     else:
-        check(load().csmae_attn_bwd_q(dt(qkv), B, T, H, hd, _p(qkv), _p(out), _p(dout), _p(lse), None if skip_out else _p(dqkv), *_emit_args(emit), st if st is not None else stream()),
+        check(load().csmae_attn_bwd_q(dt(qkv), B, T, H, hd, _p(qkv), _p(out), _p(dout), _p(lse), None if skip_out else _p(dqkv), *_emit_args(emit), _s(st)),
               "csmae_attn_bwd_q")
 
 
@@ -397,7 +395,7 @@ def layernorm_fwd(x, gamma, beta, y, mean, rstd, y32=None, eps=1e-6, emit=None, 
     M, D = x.shape
     assert not skip_out or emit is not None
     check(load().csmae_layernorm_fwd(dt(x), dt(y), M, D, _p(x), _p(gamma), _p(beta), eps, None if skip_out else _p(y), _p(y32), _p(mean), _p(rstd), *_emit_args(emit),
-                                     st if st is not None else stream()), "csmae_layernorm_fwd")
+                                     _s(st)), "csmae_layernorm_fwd")
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx_out, dgamma, dbeta, dres_in=None, dx_lp=None, partial_ws=None, emit=None, st=None):
@@ -406,72 +404,62 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dx_out, dgamma, dbeta, dres_in=None,
     M, D = x.shape
     assert dx_out.dtype == x.dtype and (dres_in is None or dres_in.dtype == x.dtype)
     lp = dt(dx_lp) if dx_lp is not None else dt(dy)
-    check(load().csmae_layernorm_bwd(dt(dy), dt(x), lp, M, D, _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dres_in), _p(dx_out), _p(dx_lp),
-                                     _p(dgamma), _p(dbeta), _p(partial_ws), partial_ws.numel() if partial_ws is not None else 0, *_emit_args(emit),
-                                     st if st is not None else stream()), "csmae_layernorm_bwd")
+    check(load().csmae_layernorm_bwd(dt(dy), dt(x), lp, M, D, _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dres_in), _p(dx_out), _p(dx_lp), _p(dgamma), _p(dbeta),
+                                     _p(partial_ws), partial_ws.numel() if partial_ws is not None else 0, *_emit_args(emit), _s(st)), "csmae_layernorm_bwd")
 
 
 def ln_param_reduce(count, M, D, partials, goff, gbase, st=None):
     """partials [>= count, slice] fp32 (row k = LayerNorm k's partial rows), goff [count, 2] int64 offsets of dgamma / dbeta in gbase."""
-    check(load().csmae_ln_param_reduce(count, M, D, _p(partials), partials.stride(0), partials.shape[1], _p(gbase), _p(goff),
-                                       st if st is not None else stream()), "csmae_ln_param_reduce")
+    check(load().csmae_ln_param_reduce(count, M, D, _p(partials), partials.stride(0), partials.shape[1], _p(gbase), _p(goff), _s(st)), "csmae_ln_param_reduce")
 
 
 def ln_param_reduce_rows(count, rows, D, partials, goff, gbase, st=None):
     """The same fold for LayerNorms whose partial rows were left by gemm_ln_bwd: `rows` = ceil(M / 128) rows per LayerNorm."""
-    check(load().csmae_ln_param_reduce_rows(count, rows, D, _p(partials), partials.stride(0), _p(gbase), _p(goff), st if st is not None else stream()),
-          "csmae_ln_param_reduce_rows")
+    check(load().csmae_ln_param_reduce_rows(count, rows, D, _p(partials), partials.stride(0), _p(gbase), _p(goff), _s(st)), "csmae_ln_param_reduce_rows")
 
 
 def bnrelu_fwd(u, gamma, beta, r, mean, rstd, N, L, running_mean=None, running_var=None, nbt=None, eps=1e-5, momentum=0.1, training=True, st=None):
     check(load().csmae_bnrelu_fwd(dt(u), N, L, u.shape[1], _p(u), _p(gamma), _p(beta), eps, momentum, _p(r), _p(mean), _p(rstd),
-                                  _p(running_mean), _p(running_var), _p(nbt), int(training), st if st is not None else stream()), "csmae_bnrelu_fwd")
+                                  _p(running_mean), _p(running_var), _p(nbt), int(training), _s(st)), "csmae_bnrelu_fwd")
 
 
 def bnrelu_bwd(u, dr, gamma, beta, mean, rstd, du, dgamma, dbeta, N, L, st=None):
     check(load().csmae_bnrelu_bwd(dt(u), N, L, u.shape[1], _p(u), _p(dr), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(du), _p(dgamma),
-                                  _p(dbeta), st if st is not None else stream()), "csmae_bnrelu_bwd")
+                                  _p(dbeta), _s(st)), "csmae_bnrelu_bwd")
 
 
 def crop_resize(src, dst, box, st=None):
     S = src.shape[-1]
-    check(load().csmae_crop_resize(src.numel() // (S * S), S, _p(src), _p(dst), _p(box), st if st is not None else stream()), "csmae_crop_resize")
+    check(load().csmae_crop_resize(src.numel() // (S * S), S, _p(src), _p(dst), _p(box), _s(st)), "csmae_crop_resize")
 
 
 def mask_sort(noise, keep, ids_restore, mask, ids_keep, ids_shuffle=None, st=None):
     rows, L = noise.shape
-    check(load().csmae_mask_sort(rows, L, keep, _p(noise), _p(ids_restore), _p(mask), _p(ids_keep), _p(ids_shuffle),
-                                 st if st is not None else stream()), "csmae_mask_sort")
+    check(load().csmae_mask_sort(rows, L, keep, _p(noise), _p(ids_restore), _p(mask), _p(ids_keep), _p(ids_shuffle), _s(st)), "csmae_mask_sort")
 
 
 def patch_gather(img0, img1, ids_keep, out, N, C, S, p, keep, st=None):
-    check(load().csmae_patch_gather(dt(out), out.shape[0], keep, N, C, S, p, _p(img0), _p(img1), _p(ids_keep), _p(out), out.stride(0),
-                                    st if st is not None else stream()), "csmae_patch_gather")
+    check(load().csmae_patch_gather(dt(out), out.shape[0], keep, N, C, S, p, _p(img0), _p(img1), _p(ids_keep), _p(out), out.stride(0), _s(st)), "csmae_patch_gather")
 
 
 def embed_assemble(tok, pos, cls, ids_keep, x, B2, keep, st=None):
-    check(load().csmae_embed_assemble(dt(x), B2, keep, x.shape[-1], _p(tok), _p(pos), _p(cls), _p(ids_keep), _p(x),
-                                      st if st is not None else stream()), "csmae_embed_assemble")
+    check(load().csmae_embed_assemble(dt(x), B2, keep, x.shape[-1], _p(tok), _p(pos), _p(cls), _p(ids_keep), _p(x), _s(st)), "csmae_embed_assemble")
 
 
 def embed_assemble_bwd(dx, dtok, dcls, B2, keep, st=None):
-    check(load().csmae_embed_assemble_bwd(dt(dx), dt(dtok), B2, keep, dx.shape[-1], _p(dx), _p(dtok), _p(dcls), st if st is not None else stream()),
-          "csmae_embed_assemble_bwd")
+    check(load().csmae_embed_assemble_bwd(dt(dx), dt(dtok), B2, keep, dx.shape[-1], _p(dx), _p(dtok), _p(dcls), _s(st)), "csmae_embed_assemble_bwd")
 
 
 def unshuffle_fwd(z, mask_token, dpos, ids_restore, xd, B2, L, keep, st=None):
-    check(load().csmae_unshuffle_fwd(dt(xd), B2, L, keep, xd.shape[-1], _p(z), _p(mask_token), _p(dpos), _p(ids_restore), _p(xd),
-                                     st if st is not None else stream()), "csmae_unshuffle_fwd")
+    check(load().csmae_unshuffle_fwd(dt(xd), B2, L, keep, xd.shape[-1], _p(z), _p(mask_token), _p(dpos), _p(ids_restore), _p(xd), _s(st)), "csmae_unshuffle_fwd")
 
 
 def unshuffle_bwd(dxd, ids_restore, dz, dmask_token, B2, L, keep, st=None):
-    check(load().csmae_unshuffle_bwd(dt(dxd), dt(dz), B2, L, keep, dxd.shape[-1], _p(dxd), _p(ids_restore), _p(dz), _p(dmask_token),
-                                     st if st is not None else stream()), "csmae_unshuffle_bwd")
+    check(load().csmae_unshuffle_bwd(dt(dxd), dt(dz), B2, L, keep, dxd.shape[-1], _p(dxd), _p(ids_restore), _p(dz), _p(dmask_token), _s(st)), "csmae_unshuffle_bwd")
 
 
 def rows_gather(src, dst, group, gstride, off, st=None):
-    check(load().csmae_rows_gather(dt(dst), dst.shape[0], dst.shape[1], _p(src), group, gstride, off, _p(dst), st if st is not None else stream()),
-          "csmae_rows_gather")
+    check(load().csmae_rows_gather(dt(dst), dst.shape[0], dst.shape[1], _p(src), group, gstride, off, _p(dst), _s(st)), "csmae_rows_gather")
 
 
 def rows_gather_idx(x, ids, keep, out, st=None):
@@ -479,7 +467,7 @@ def rows_gather_idx(x, ids, keep, out, st=None):
     N, L, D = x.shape
     assert x.dtype == out.dtype == torch.float32 and ids.dtype == torch.int32 and x.is_contiguous() and out.is_contiguous() and ids.stride(1) == 1
     assert out.shape == (N, keep, D) and ids.shape[0] == N and ids.shape[1] >= keep
-    check(load().csmae_rows_gather_idx(N, L, keep, D, _p(x), _p(ids), ids.stride(0), _p(out), st if st is not None else stream()), "csmae_rows_gather_idx")
+    check(load().csmae_rows_gather_idx(N, L, keep, D, _p(x), _p(ids), ids.stride(0), _p(out), _s(st)), "csmae_rows_gather_idx")
     return out
 
 
@@ -487,7 +475,7 @@ def rows_scatter_add2(a, scale_a, off_a, b, scale_b, off_b, dst, group, gstride,
     """dst[view(r) + off_a] += scale_a * a[r]; dst[view(r) + off_b] += scale_b * b[r]   (view(r) = (r // group) * gstride + r % group)."""
     assert a.shape == b.shape and a.dtype == b.dtype and dst.dtype == torch.float32
     check(load().csmae_rows_scatter_add2(dt(a), a.shape[0], a.shape[1], _p(a), scale_a, off_a, _p(b), scale_b, off_b, group, gstride, _p(dst),
-                                         st if st is not None else stream()), "csmae_rows_scatter_add2")
+                                         _s(st)), "csmae_rows_scatter_add2")
 
 
 def spec_fixup(g, bufs, tmp, dgamma, dbeta, st=None):
@@ -495,29 +483,26 @@ def spec_fixup(g, bufs, tmp, dgamma, dbeta, st=None):
     b0, b1, b2 = bufs
     assert all(b.dtype == torch.bfloat16 and b.is_contiguous() for b in bufs) and tmp.shape[0] == 2 and tmp.dtype == torch.float32
     check(load().csmae_spec_fixup(_p(g), _p(b0), b0.numel(), _p(b1), b1.numel(), _p(b2), b2.numel(), _p(tmp[0]), _p(tmp[1]), _p(dgamma), _p(dbeta), tmp.shape[1],
-                                  st if st is not None else stream()), "csmae_spec_fixup")
+                                  _s(st)), "csmae_spec_fixup")
 
 
 def rows_scatter_add(src, dst, group, gstride, off, scale=1.0, st=None):
-    check(load().csmae_rows_scatter_add(dt(src), src.shape[0], src.shape[1], _p(src), scale, group, gstride, off, _p(dst),
-                                        st if st is not None else stream()), "csmae_rows_scatter_add")
+    check(load().csmae_rows_scatter_add(dt(src), src.shape[0], src.shape[1], _p(src), scale, group, gstride, off, _p(dst), _s(st)), "csmae_rows_scatter_add")
 
 
 def target_minmax(img0, img1, scratch, out, B2, N, C, S, p, norm_pix, st=None):
-    check(load().csmae_target_minmax(int(norm_pix), B2, N, C, S, p, _p(img0), _p(img1), _p(scratch), _p(out), st if st is not None else stream()),
-          "csmae_target_minmax")
+    check(load().csmae_target_minmax(int(norm_pix), B2, N, C, S, p, _p(img0), _p(img1), _p(scratch), _p(out), _s(st)), "csmae_target_minmax")
 
 
 def recon_loss_fwd(kind, norm_pix, img0, img1, pred, minmax, rowloss, B2, N, C, S, p, mask=None, st=None):
     """pred: fp32 or bf16 [B2 * (L + 1), >= P]; mask (optional, [B2 * L] fp32): patches with mask 0 are skipped (rowloss 0)."""
     check(load().csmae_recon_loss_fwd(LOSS_KINDS[kind], int(norm_pix), dt(pred), B2, N, C, S, p, _p(img0), _p(img1), _p(pred), pred.stride(0), _p(minmax),
-                                      _p(mask), _p(rowloss), st if st is not None else stream()), "csmae_recon_loss_fwd")
+                                      _p(mask), _p(rowloss), _s(st)), "csmae_recon_loss_fwd")
 
 
 def recon_loss_bwd(kind, norm_pix, img0, img1, pred, minmax, mask, losses, gout, vscale, dpred, B2, N, C, S, p, extra=None, st=None):
-    check(load().csmae_recon_loss_bwd(LOSS_KINDS[kind], int(norm_pix), dt(dpred), dt(pred), B2, N, C, S, p, _p(img0), _p(img1), _p(pred), pred.stride(0),
-                                      _p(minmax), _p(mask), _p(losses), _p(gout), vscale, _p(extra), _p(dpred), dpred.stride(0),
-                                      st if st is not None else stream()), "csmae_recon_loss_bwd")
+    check(load().csmae_recon_loss_bwd(LOSS_KINDS[kind], int(norm_pix), dt(dpred), dt(pred), B2, N, C, S, p, _p(img0), _p(img1), _p(pred), pred.stride(0), _p(minmax),
+                                      _p(mask), _p(losses), _p(gout), vscale, _p(extra), _p(dpred), dpred.stride(0), _s(st)), "csmae_recon_loss_bwd")
 
 
 # ---- ssim family (SURVEY §8 f-4; MAE_ViT_Shared.py:165-267)
@@ -529,82 +514,73 @@ def ssim_workspace_floats(B2, C, S, p, levels):
 
 def ssim_fwd(levels, norm_pix, img0, img1, pred, mask, ws, terms, B2, N, C, S, p, flags=0, st=None):
     check(load().csmae_ssim_fwd(levels, flags, int(norm_pix), B2, N, C, S, p, _p(img0), _p(img1), _p(pred), pred.stride(0), _p(mask), _p(ws), _p(terms),
-                                st if st is not None else stream()), "csmae_ssim_fwd")
+                                _s(st)), "csmae_ssim_fwd")
 
 
 def ssim_apply(pure, views, weight, recon_scale, terms, losses, st=None):
-    check(load().csmae_ssim_apply(int(pure), views, weight, recon_scale, _p(terms), _p(losses), st if st is not None else stream()), "csmae_ssim_apply")
+    check(load().csmae_ssim_apply(int(pure), views, weight, recon_scale, _p(terms), _p(losses), _s(st)), "csmae_ssim_apply")
 
 
 def ssim_bwd(levels, pred, mask, gout, scale, ws, extra, B2, N, C, S, p, st=None):
-    check(load().csmae_ssim_bwd(levels, B2, N, C, S, p, _p(pred), pred.stride(0), _p(mask), _p(gout), scale, _p(ws), _p(extra),
-                                st if st is not None else stream()), "csmae_ssim_bwd")
+    check(load().csmae_ssim_bwd(levels, B2, N, C, S, p, _p(pred), pred.stride(0), _p(mask), _p(gout), scale, _p(ws), _p(extra), _s(st)), "csmae_ssim_bwd")
 
 
 def pair_loss_fwd(kind, rows, D, a, aview, t, tview, partial, st=None):
-    check(load().csmae_pair_loss_fwd(LOSS_KINDS[kind], rows, D, _p(a), *aview, _p(t), *tview, _p(partial), st if st is not None else stream()),
-          "csmae_pair_loss_fwd")
+    check(load().csmae_pair_loss_fwd(LOSS_KINDS[kind], rows, D, _p(a), *aview, _p(t), *tview, _p(partial), _s(st)), "csmae_pair_loss_fwd")
 
 
 def pair_loss_bwd(kind, rows, D, a, aview, t, tview, gout, coef, da_lp=None, da_acc=None, dt_acc=None, lp_dtype=F32, st=None):
     lp = dt(da_lp) if da_lp is not None else lp_dtype
     check(load().csmae_pair_loss_bwd(LOSS_KINDS[kind], lp, rows, D, _p(a), *aview, _p(t), *tview, _p(gout), coef, _p(da_lp), _p(da_acc), _p(dt_acc),
-                                     st if st is not None else stream()), "csmae_pair_loss_bwd")
+                                     _s(st)), "csmae_pair_loss_bwd")
 
 
 def ntxent_fwd(latent, z, inv_norm, E, neg, rowloss, N, Te, keep, tau=0.5, eps=1e-8, st=None):
-    check(load().csmae_ntxent_fwd(N, Te, keep, latent.shape[-1], _p(latent), tau, eps, _p(z), _p(inv_norm), _p(E), _p(neg), _p(rowloss),
-                                  st if st is not None else stream()), "csmae_ntxent_fwd")
+    check(load().csmae_ntxent_fwd(N, Te, keep, latent.shape[-1], _p(latent), tau, eps, _p(z), _p(inv_norm), _p(E), _p(neg), _p(rowloss), _s(st)), "csmae_ntxent_fwd")
 
 
 def ntxent_bwd(z, inv_norm, E, neg, gout, dpool, N, tau=0.5, eps=1e-8, st=None):
-    check(load().csmae_ntxent_bwd(N, z.shape[-1], _p(z), _p(inv_norm), _p(E), _p(neg), tau, eps, _p(gout), _p(dpool), st if st is not None else stream()),
-          "csmae_ntxent_bwd")
+    check(load().csmae_ntxent_bwd(N, z.shape[-1], _p(z), _p(inv_norm), _p(E), _p(neg), tau, eps, _p(gout), _p(dpool), _s(st)), "csmae_ntxent_bwd")
 
 
 def latent_grad_finish(dlat, dpool, inv_keep, dlat_lp, B2, Te, st=None):
     lp = dt(dlat_lp) if dlat_lp is not None else F32
-    check(load().csmae_latent_grad_finish(lp, B2, Te, dlat.shape[-1], _p(dlat), _p(dpool), inv_keep, _p(dlat_lp), st if st is not None else stream()),
-          "csmae_latent_grad_finish")
+    check(load().csmae_latent_grad_finish(lp, B2, Te, dlat.shape[-1], _p(dlat), _p(dpool), inv_keep, _p(dlat_lp), _s(st)), "csmae_latent_grad_finish")
 
 
 def loss_finalize(per_view, views, rowloss, mask, recon_scale, losses, cd_partial=None, cd_scale=0.0, e_partial=None, e_scale=0.0,
                   ce_rowloss=None, ce_rows=0, st=None):
     check(load().csmae_loss_finalize(per_view, views, _p(rowloss), _p(mask), recon_scale, _p(cd_partial), cd_scale, _p(e_partial), e_scale,
-                                     _p(ce_rowloss), ce_rows, _p(losses), st if st is not None else stream()), "csmae_loss_finalize")
+                                     _p(ce_rowloss), ce_rows, _p(losses), _s(st)), "csmae_loss_finalize")
 
 
 def adamw(tile_off, tile_cnt, tile_wd, p, g, m, v, lr, beta1, beta2, eps, step, p_lp=None, gate=None, tile_ks=None, p_ks=None, st=None):
     """One fused AdamW step over the tiles; `step` (1-based) sets the bias corrections 1 - beta^step; a non-finite `gate` (device
     scalar) turns the launch into a no-op.  tile_ks (int64 [ntiles, 3]: weight offset, N, K; K = 0 none) + p_ks: also write the K-slab mirrors."""
-    check(load().csmae_adamw(tile_off.numel(), _p(tile_off), _p(tile_cnt), _p(tile_wd), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1),
-                             float(beta2), float(eps), 1.0 - beta1 ** step, 1.0 - beta2 ** step, _p(p_lp), _p(gate), _p(tile_ks), _p(p_ks),
-                             st if st is not None else stream()), "csmae_adamw")
+    check(load().csmae_adamw(tile_off.numel(), _p(tile_off), _p(tile_cnt), _p(tile_wd), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2), float(eps),
+                             1.0 - beta1 ** step, 1.0 - beta2 ** step, _p(p_lp), _p(gate), _p(tile_ks), _p(p_ks), _s(st)), "csmae_adamw")
 
 
 def adamw_fp8(tile8, wd, p, g, m, v, lr, beta1, beta2, eps, step, p_lp, gate, w8, w8t, amax_prev, amax_next, dq, st=None):
     """The fused AdamW step over 64 x 64 sub-blocks of fp8-mirrored weights (tile8 int64 [ntiles, 6]), writing W8 / W8^T with delayed scaling (csmae_adamw_fp8)."""
-    check(load().csmae_adamw_fp8(tile8.shape[0], _p(tile8), float(wd), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2), float(eps),
-                                 1.0 - beta1 ** step, 1.0 - beta2 ** step, _p(p_lp), _p(gate), _p(w8), _p(w8t), _p(amax_prev), _p(amax_next), _p(dq),
-                                 st if st is not None else stream()), "csmae_adamw_fp8")
+    check(load().csmae_adamw_fp8(tile8.shape[0], _p(tile8), float(wd), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2), float(eps), 1.0 - beta1 ** step,
+                                 1.0 - beta2 ** step, _p(p_lp), _p(gate), _p(w8), _p(w8t), _p(amax_prev), _p(amax_next), _p(dq), _s(st)), "csmae_adamw_fp8")
 
 
 def gate_accumulate(loss, slot, accumulate, st=None):
-    check(load().csmae_gate_accumulate(_p(loss), _p(slot), int(accumulate), st if st is not None else stream()), "csmae_gate_accumulate")
+    check(load().csmae_gate_accumulate(_p(loss), _p(slot), int(accumulate), _s(st)), "csmae_gate_accumulate")
 
 
 def clip_grad_norm(g, max_norm, scratch, out, st=None):
     """out[0] = ||g||_2, out[1] = min(1, max_norm / (norm + 1e-6)); g *= out[1] in place (max_norm <= 0: norm only)."""
-    check(load().csmae_clip_grad_norm(g.numel(), _p(g), float(max_norm), _p(scratch), _p(out), st if st is not None else stream()),
-          "csmae_clip_grad_norm")
+    check(load().csmae_clip_grad_norm(g.numel(), _p(g), float(max_norm), _p(scratch), _p(out), _s(st)), "csmae_clip_grad_norm")
 
 
 def augment_u8(src, meta, mean, inv_std, dst, st=None):
     """src [N, Hmax, Wmax, C] uint8, meta [N, 8] int32 {H, W, i, j, h, w, hflip, vflip}, dst [N, C, S, S] fp32 (util/datasets.py:120-136)."""
     N, Hmax, Wmax, C = src.shape
     assert src.dtype == torch.uint8 and src.is_contiguous() and meta.dtype == torch.int32 and meta.shape == (N, 8) and dst.shape[:2] == (N, C)
-    check(load().csmae_augment_u8(N, C, Hmax, Wmax, dst.shape[-1], _p(src), _p(meta), _p(mean), _p(inv_std), _p(dst),
-                                  st if st is not None else stream()), "csmae_augment_u8")
+    check(load().csmae_augment_u8(N, C, Hmax, Wmax, dst.shape[-1], _p(src), _p(meta), _p(mean), _p(inv_std), _p(dst), _s(st)), "csmae_augment_u8")
 
 
 def eval_u8(src, meta, mean, inv_std, dst, st=None):
@@ -613,20 +589,19 @@ def eval_u8(src, meta, mean, inv_std, dst, st=None):
     N, Hmax, Wmax, C = src.shape
     assert src.dtype == torch.uint8 and src.is_contiguous() and meta.dtype == torch.int32 and meta.shape == (N, 8) and dst.shape[:2] == (N, C)
     assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.shape[-1] == dst.shape[-2]
-    check(load().csmae_eval_u8(N, C, Hmax, Wmax, dst.shape[-1], _p(src), _p(meta), _p(mean), _p(inv_std), _p(dst),
-                               st if st is not None else stream()), "csmae_eval_u8")
+    check(load().csmae_eval_u8(N, C, Hmax, Wmax, dst.shape[-1], _p(src), _p(meta), _p(mean), _p(inv_std), _p(dst), _s(st)), "csmae_eval_u8")
 
 
 def cast_bf16(src, dst, st=None):
-    check(load().csmae_cast_f32_to_bf16(src.numel(), _p(src), _p(dst), st if st is not None else stream()), "csmae_cast_f32_to_bf16")
+    check(load().csmae_cast_f32_to_bf16(src.numel(), _p(src), _p(dst), _s(st)), "csmae_cast_f32_to_bf16")
 
 
 def cast_f32(src, dst, st=None):
-    check(load().csmae_cast_bf16_to_f32(src.numel(), _p(src), _p(dst), st if st is not None else stream()), "csmae_cast_bf16_to_f32")
+    check(load().csmae_cast_bf16_to_f32(src.numel(), _p(src), _p(dst), _s(st)), "csmae_cast_bf16_to_f32")
 
 
 def colsum(x, out, st=None):
-    check(load().csmae_colsum(dt(x), x.shape[0], x.shape[1], _p(x), x.stride(0), _p(out), st if st is not None else stream()), "csmae_colsum")
+    check(load().csmae_colsum(dt(x), x.shape[0], x.shape[1], _p(x), x.stride(0), _p(out), _s(st)), "csmae_colsum")
 
 
 # ---- linear probing (csrc/classify.hip): everything behind the last transformer block, fp32
@@ -640,8 +615,7 @@ def probe_pool_fwd(x, gamma, beta, feat, global_pool, eps=1e-6, st=None):
     N, T, D = x.shape
     assert x.is_contiguous() and feat.shape == (N, D) and gamma.numel() == D and beta.numel() == D
     _f32c(gamma, beta, feat)
-    check(load().csmae_probe_pool_fwd(dt(x), int(bool(global_pool)), N, T, D, _p(x), _p(gamma), _p(beta), float(eps), _p(feat),
-                                      st if st is not None else stream()), "csmae_probe_pool_fwd")
+    check(load().csmae_probe_pool_fwd(dt(x), int(bool(global_pool)), N, T, D, _p(x), _p(gamma), _p(beta), float(eps), _p(feat), _s(st)), "csmae_probe_pool_fwd")
     return feat
 
 
@@ -653,7 +627,7 @@ def bn1d_fwd(feat, fbn, running_mean, running_var, nbt=None, eps=1e-6, momentum=
     assert fbn.shape == feat.shape and running_mean.numel() == D and running_var.numel() == D and (nbt is None or nbt.dtype == torch.int64)
     _f32c(feat, fbn, running_mean, running_var)
     check(load().csmae_bn1d_fwd(N, D, _p(feat), float(eps), float(momentum), _p(fbn), _p(running_mean), _p(running_var), _p(nbt), int(bool(training)),
-                                st if st is not None else stream()), "csmae_bn1d_fwd")
+                                _s(st)), "csmae_bn1d_fwd")
     return fbn
 
 
@@ -662,7 +636,7 @@ def head_linear_fwd(x, w, b, logits, st=None):
     (N, D), K = x.shape, w.shape[0]
     assert w.shape == (K, D) and logits.shape == (N, K) and (b is None or b.numel() == K)
     _f32c(x, w, b, logits)
-    check(load().csmae_head_linear_fwd(N, D, K, _p(x), _p(w), _p(b), _p(logits), st if st is not None else stream()), "csmae_head_linear_fwd")
+    check(load().csmae_head_linear_fwd(N, D, K, _p(x), _p(w), _p(b), _p(logits), _s(st)), "csmae_head_linear_fwd")
     return logits
 
 
@@ -671,8 +645,7 @@ def head_linear_bwd(dlogits, x, dw, db=None, accumulate=False, gscale=None, st=N
     (N, K), D = dlogits.shape, x.shape[1]
     assert x.shape == (N, D) and dw.shape == (K, D) and (db is None or db.numel() == K)
     _f32c(dlogits, x, dw, db, gscale)
-    check(load().csmae_head_linear_bwd(N, D, K, _p(dlogits), _p(x), _p(gscale), _p(dw), _p(db), int(bool(accumulate)),
-                                       st if st is not None else stream()), "csmae_head_linear_bwd")
+    check(load().csmae_head_linear_bwd(N, D, K, _p(dlogits), _p(x), _p(gscale), _p(dw), _p(db), int(bool(accumulate)), _s(st)), "csmae_head_linear_bwd")
 
 
 def softmax_ce(logits, labels, loss, dlogits=None, counts=None, gout=None, accumulate_counts=False, scratch=None, st=None):
@@ -684,7 +657,7 @@ def softmax_ce(logits, labels, loss, dlogits=None, counts=None, gout=None, accum
         scratch = torch.empty(3 * N, device=logits.device, dtype=torch.float32)
     assert scratch.numel() >= 3 * N
     check(load().csmae_softmax_ce(N, K, _p(logits), _p(labels), _p(gout), _p(scratch), _p(loss), _p(dlogits), _p(counts), int(bool(accumulate_counts)),
-                                  st if st is not None else stream()), "csmae_softmax_ce")
+                                  _s(st)), "csmae_softmax_ce")
 
 
 LARS_NORM_FLOATS = 128   # scratch floats per tensor of a csmae_lars_step launch
@@ -704,8 +677,7 @@ def lars_step(table, norms, lr, weight_decay, momentum, trust_coefficient, gate=
     n = table.shape[0]
     assert table.dtype == torch.int64 and table.shape[1] == 5 and table.is_contiguous() and norms.numel() >= n * LARS_NORM_FLOATS
     _f32c(norms, gate)
-    check(load().csmae_lars_step(n, _p(table), float(lr), float(weight_decay), float(momentum), float(trust_coefficient), _p(norms), _p(gate),
-                                 st if st is not None else stream()), "csmae_lars_step")
+    check(load().csmae_lars_step(n, _p(table), float(lr), float(weight_decay), float(momentum), float(trust_coefficient), _p(norms), _p(gate), _s(st)), "csmae_lars_step")
 
 
 # ---- end-to-end fine-tuning (csrc/classify.hip)
@@ -721,7 +693,7 @@ def probe_pool_bwd(x, dfeat, gamma, dres, dgamma, dbeta, global_pool, eps=1e-6, 
         partial = torch.empty(2 * N * D, device=x.device, dtype=torch.float32)
     assert partial.numel() >= 2 * N * D
     check(load().csmae_probe_pool_bwd(dt(x), int(bool(global_pool)), N, T, D, _p(x), _p(dfeat), _p(gamma), float(eps), _p(dres), _p(partial), _p(dgamma),
-                                      _p(dbeta), int(bool(accumulate)), st if st is not None else stream()), "csmae_probe_pool_bwd")
+                                      _p(dbeta), int(bool(accumulate)), _s(st)), "csmae_probe_pool_bwd")
     return dres
 
 
@@ -730,7 +702,7 @@ def head_linear_dx(dlogits, w, dx, gscale=None, st=None):
     (N, K), D = dlogits.shape, w.shape[1]
     assert w.shape == (K, D) and dx.shape == (N, D)
     _f32c(dlogits, w, dx, gscale)
-    check(load().csmae_head_linear_dx(N, D, K, _p(dlogits), _p(w), _p(gscale), _p(dx), st if st is not None else stream()), "csmae_head_linear_dx")
+    check(load().csmae_head_linear_dx(N, D, K, _p(dlogits), _p(w), _p(gscale), _p(dx), _s(st)), "csmae_head_linear_dx")
     return dx
 
 
@@ -742,7 +714,7 @@ def soft_ce(logits, target, loss, dlogits=None, gout=None, scratch=None, st=None
     if scratch is None:
         scratch = torch.empty(N, device=logits.device, dtype=torch.float32)
     assert scratch.numel() >= N
-    check(load().csmae_soft_ce(N, K, _p(logits), _p(target), _p(gout), _p(scratch), _p(loss), _p(dlogits), st if st is not None else stream()), "csmae_soft_ce")
+    check(load().csmae_soft_ce(N, K, _p(logits), _p(target), _p(gout), _p(scratch), _p(loss), _p(dlogits), _s(st)), "csmae_soft_ce")
 
 
 def mixup_target(labels, target, lam=1.0, smoothing=0.0, st=None):
@@ -750,7 +722,7 @@ def mixup_target(labels, target, lam=1.0, smoothing=0.0, st=None):
     N, K = target.shape
     assert labels.dtype == torch.int64 and labels.numel() == N and labels.is_contiguous()
     _f32c(target)
-    check(load().csmae_mixup_target(N, K, _p(labels), float(lam), float(smoothing), _p(target), st if st is not None else stream()), "csmae_mixup_target")
+    check(load().csmae_mixup_target(N, K, _p(labels), float(lam), float(smoothing), _p(target), _s(st)), "csmae_mixup_target")
     return target
 
 
@@ -762,8 +734,7 @@ def mixup_cutmix(x, out, lam=1.0, box=None, st=None):
     assert out.shape == x.shape and out.data_ptr() != x.data_ptr()
     _f32c(x, out)
     yl, yh, xl, xh = (0, 0, 0, 0) if box is None else (int(v) for v in box)
-    check(load().csmae_mixup_cutmix(int(box is not None), N, C, H, W, _p(x), _p(out), float(lam), yl, yh, xl, xh, st if st is not None else stream()),
-          "csmae_mixup_cutmix")
+    check(load().csmae_mixup_cutmix(int(box is not None), N, C, H, W, _p(x), _p(out), float(lam), yl, yh, xl, xh, _s(st)), "csmae_mixup_cutmix")
     return out
 
 
@@ -772,7 +743,7 @@ def pos_embed_grad(dres, dpos, accumulate=False, st=None):
     N, T, D = dres.shape
     assert dres.is_contiguous() and dpos.numel() == T * D
     _f32c(dpos)
-    check(load().csmae_pos_embed_grad(dt(dres), N, T, D, _p(dres), _p(dpos), int(bool(accumulate)), st if st is not None else stream()), "csmae_pos_embed_grad")
+    check(load().csmae_pos_embed_grad(dt(dres), N, T, D, _p(dres), _p(dpos), int(bool(accumulate)), _s(st)), "csmae_pos_embed_grad")
 
 
 # ---- k-NN evaluation (csrc/knn.hip)
@@ -780,8 +751,7 @@ def l2_normalize(src, dst, eps=1e-12, st=None):
     """dst [rows, D] (contiguous, fp32 or bf16) = src[r] / max(||src[r]||, eps); src fp32 [rows, D], rows may be strided."""
     rows, D = src.shape
     assert src.dtype == torch.float32 and src.stride(1) == 1 and dst.shape == (rows, D) and dst.is_contiguous()
-    check(load().csmae_l2_normalize(dt(src), dt(dst), rows, D, _p(src), src.stride(0), float(eps), _p(dst), st if st is not None else stream()),
-          "csmae_l2_normalize")
+    check(load().csmae_l2_normalize(dt(src), dt(dst), rows, D, _p(src), src.stride(0), float(eps), _p(dst), _s(st)), "csmae_l2_normalize")
     return dst
 
 
@@ -792,11 +762,10 @@ def knn_select(sim, val, idx, base=0, Bc=None, st=None):
     Bc = sim.shape[1] if Bc is None else int(Bc)
     assert sim.dtype == torch.float32 and sim.shape[0] == Q and sim.stride(1) == 1 and 0 < Bc <= sim.shape[1]
     assert val.dtype == torch.float32 and idx.dtype == torch.int32 and idx.shape == val.shape and val.is_contiguous() and idx.is_contiguous()
-    if _timer is not None:
-        _timer.begin()
-    check(load().csmae_knn_select(Q, Bc, k, _p(sim), sim.stride(0), int(base), _p(val), _p(idx), st if st is not None else stream()), "csmae_knn_select")
-    if _timer is not None:
-        _timer.end("knn_select", 4.0 * Q * Bc)   # work: the bytes of the tile
+    t = _begin()
+    check(load().csmae_knn_select(Q, Bc, k, _p(sim), sim.stride(0), int(base), _p(val), _p(idx), _s(st)), "csmae_knn_select")
+    if t:
+        t.end("knn_select", 4.0 * Q * Bc)   # work: the bytes of the tile
 
 
 def knn_vote(val, idx, bank_labels, num_classes, T, top5, votes=None, counts=None, query_labels=None, accumulate_counts=False, st=None):
@@ -810,7 +779,7 @@ def knn_vote(val, idx, bank_labels, num_classes, T, top5, votes=None, counts=Non
     assert query_labels is None or (query_labels.dtype == torch.int64 and query_labels.numel() == Q and query_labels.is_contiguous() and counts is not None)
     _f32c(votes, counts)
     check(load().csmae_knn_vote(Q, k, K, _p(val), _p(idx), _p(bank_labels), 1.0 / float(T), _p(votes), _p(top5), _p(counts), _p(query_labels),
-                                int(bool(accumulate_counts)), st if st is not None else stream()), "csmae_knn_vote")
+                                int(bool(accumulate_counts)), _s(st)), "csmae_knn_vote")
 
 
 # ---- per-image reconstruction scores (csrc/recon_eval.hip)
@@ -836,12 +805,11 @@ def recon_eval(img, pred, mean, std, p, out=None, st=None, ws=None):
     floats = recon_eval_workspace_floats(N, C, S)
     part = ws if ws is not None else torch.empty(floats, device=img.device, dtype=torch.float32)
     assert part.dtype == torch.float32 and part.is_contiguous() and part.numel() >= floats
-    if _timer is not None:
-        _timer.begin()
+    t = _begin()
     check(load().csmae_recon_eval(_DT.get(pred.dtype, -1), N, C, S, p, _p(img), _p(pred), pred.stride(1), pred.stride(0), _p(mean), _p(std), _p(part), _p(out),
-                                  st if st is not None else stream()), "csmae_recon_eval")
-    if _timer is not None:
-        _timer.end("recon_eval", (4.0 + pred.element_size()) * N * C * S * S)   # work: the bytes of both operands
+                                  _s(st)), "csmae_recon_eval")
+    if t:
+        t.end("recon_eval", (4.0 + pred.element_size()) * N * C * S * S)   # work: the bytes of both operands
     return out
 
 

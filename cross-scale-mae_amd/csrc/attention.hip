@@ -911,20 +911,19 @@ static bool bf16_resident(int T, int hd) { return hd % 8 == 0 && T <= 288 && (hd
 // ---- one routing decision for csmae_attn_fwd, csmae_attn_bwd and csmae_attn_route.  csmae_attn_stream_mode: 0 never stream (the routing before
 // the streaming family: A/B runs), 1 stream what is not resident (default), 2 stream every bf16 shape with head_dim % 8 == 0, resident ones too
 // (tests, A/B).  The fp8-emitting entry points (csmae_attn_*_q) always take the resident kernels.
-enum { ATTN_ROUTE_RESIDENT = 0, ATTN_ROUTE_STREAM = 1, ATTN_ROUTE_ANY = 2, ATTN_ROUTE_F32 = 3 };
 static int initial_stream_mode() {            // CSMAE_DEBUG=attn_stream=0|1|2 presets the mode for programs that never call the switch (bench.py A/B)
   const char* v = csmae_debug_opt("attn_stream");
   return v && v[0] >= '0' && v[0] <= '2' && !v[1] ? v[0] - '0' : 1;
 }
 static int g_attn_stream_mode = initial_stream_mode();
 static int attn_route(int dtype, int T, int hd, bool emit) {
-  if (dtype == CSMAE_F32) return ATTN_ROUTE_F32;
+  if (dtype == CSMAE_F32) return CSMAE_ATTN_ROUTE_F32;
   if (dtype != CSMAE_BF16) return CSMAE_ERR_UNSUPPORTED;
   if (T <= 0 || T > 8192 || hd <= 0 || hd > 128 || hd % 4 != 0) return CSMAE_ERR_ARG;   // (what check_common refuses)
   const bool streamable = hd % 8 == 0 && !emit;
-  if (g_attn_stream_mode == 2 && streamable) return ATTN_ROUTE_STREAM;
-  if (bf16_resident(T, hd)) return ATTN_ROUTE_RESIDENT;
-  return g_attn_stream_mode == 1 && streamable ? ATTN_ROUTE_STREAM : ATTN_ROUTE_ANY;
+  if (g_attn_stream_mode == 2 && streamable) return CSMAE_ATTN_ROUTE_STREAM;
+  if (bf16_resident(T, hd)) return CSMAE_ATTN_ROUTE_RESIDENT;
+  return g_attn_stream_mode == 1 && streamable ? CSMAE_ATTN_ROUTE_STREAM : CSMAE_ATTN_ROUTE_ANY;
 }
 extern "C" int csmae_attn_route(int dtype, int T, int hd) { return attn_route(dtype, T, hd, false); }
 extern "C" int csmae_attn_stream_mode(int mode) {
@@ -947,8 +946,8 @@ static int attn_fwd_impl(int dtype, long long B, int T, int H, int hd, const voi
   const int BH = (int)(B * H);
   if (dtype == CSMAE_BF16) {
     const int route = attn_route(dtype, T, hd, em != nullptr);
-    if (route == ATTN_ROUTE_STREAM) { if (int rs = attn_stream_fwd(B, T, H, hd, qkv, out, lse, st)) return rs; return csmae_check_launch("csmae_attn_fwd"); }
-    if (route != ATTN_ROUTE_RESIDENT) { CSMAE_REQUIRE(!em, "csmae_attn_fwd_q: the fp8 copy is emitted by the LDS-resident kernels only (csmae_attn_resident)"); launch_any<bf16_t>(false, B, T, H, D, hd, scale, qkv, nullptr, nullptr, lse, nullptr, out, st); return csmae_check_launch("csmae_attn_fwd"); }
+    if (route == CSMAE_ATTN_ROUTE_STREAM) { if (int rs = attn_stream_fwd(B, T, H, hd, qkv, out, lse, st)) return rs; return csmae_check_launch("csmae_attn_fwd"); }
+    if (route != CSMAE_ATTN_ROUTE_RESIDENT) { CSMAE_REQUIRE(!em, "csmae_attn_fwd_q: the fp8 copy is emitted by the LDS-resident kernels only (csmae_attn_resident)"); launch_any<bf16_t>(false, B, T, H, D, hd, scale, qkv, nullptr, nullptr, lse, nullptr, out, st); return csmae_check_launch("csmae_attn_fwd"); }
 #define CALLF(HDV, NK) launch_fwd_bf16<HDV, NK>(BH, qkv, out, lse, T, H, D, hd, scale, st, em)
     DISPATCH_BF16(CALLF)
 #undef CALLF
@@ -992,8 +991,8 @@ static int attn_bwd_impl(int dtype, long long B, int T, int H, int hd, const voi
   const int BH = (int)(B * H);
   if (dtype == CSMAE_BF16) {
     const int route = attn_route(dtype, T, hd, em != nullptr);
-    if (route == ATTN_ROUTE_STREAM) { if (int rs = attn_stream_bwd(B, T, H, hd, qkv, out, dout, lse, dqkv, st)) return rs; return csmae_check_launch("csmae_attn_bwd"); }
-    if (route != ATTN_ROUTE_RESIDENT) { CSMAE_REQUIRE(!em, "csmae_attn_bwd_q: the fp8 copy is emitted by the LDS-resident kernels only (csmae_attn_resident)"); launch_any<bf16_t>(true, B, T, H, D, hd, scale, qkv, out, dout, nullptr, lse, dqkv, st); return csmae_check_launch("csmae_attn_bwd"); }
+    if (route == CSMAE_ATTN_ROUTE_STREAM) { if (int rs = attn_stream_bwd(B, T, H, hd, qkv, out, dout, lse, dqkv, st)) return rs; return csmae_check_launch("csmae_attn_bwd"); }
+    if (route != CSMAE_ATTN_ROUTE_RESIDENT) { CSMAE_REQUIRE(!em, "csmae_attn_bwd_q: the fp8 copy is emitted by the LDS-resident kernels only (csmae_attn_resident)"); launch_any<bf16_t>(true, B, T, H, D, hd, scale, qkv, out, dout, nullptr, lse, dqkv, st); return csmae_check_launch("csmae_attn_bwd"); }
 #define CALLB(HDV, NK) launch_bwd_bf16<HDV, NK>(BH, qkv, out, dout, lse, dqkv, T, H, D, hd, scale, st, em)
     DISPATCH_BF16(CALLB)
 #undef CALLB

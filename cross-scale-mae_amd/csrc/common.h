@@ -5,14 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <math.h>
-
-#define CSMAE_F32 0
-#define CSMAE_BF16 1
-
-#define CSMAE_OK 0
-#define CSMAE_ERR_ARG -1
-#define CSMAE_ERR_LAUNCH -2
-#define CSMAE_ERR_UNSUPPORTED -3
+#include "../../include/csmae.h"   // the C ABI: every translation unit sees the prototypes (a definition that disagrees does not compile) and takes its dtype / status / epilogue / loss / route codes from there
 
 typedef unsigned short bf16_t;  // raw bfloat16 bits
 typedef short s4_t __attribute__((ext_vector_type(4)));
@@ -35,6 +28,7 @@ const char* csmae_debug_opt(const char* key);
 // ---- error plumbing (thread-local message; see include/csmae.h csmae_last_error)
 void csmae_set_error(const char* fmt, ...);
 int csmae_check_launch(const char* what);
+int csmae_colsum_launch(int dtype, long long M, int N, const void* x, long long ld, float* out, void* stream);   // optim.hip: csmae_colsum without the C linkage (csmae_gemm_dw's unfused bias gradient)
 // Completion event of the NEXT kernel launch of this host thread (csmae_next_launch_event).  A launch site that goes through CSMAE_LAUNCH
 // attaches the event to its dispatch packet (hipExtLaunchKernelGGL's stopEvent: the packet's own completion signal) instead of leaving the
 // caller to put a marker packet behind the kernel — a marker costs the stream it is recorded on 3-5 us (tools/event_probe.hip).

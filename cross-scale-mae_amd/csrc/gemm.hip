@@ -859,11 +859,11 @@ extern "C" int csmae_gemm_fp8(int a_fmt, long long M, long long N, long long K, 
                               const void* resid, long long ldr, const float* dq_a, const float* dq_b, void* q_out, long long ldq, int q_fmt,
                               const float* q_amax_prev, float* q_amax_next, float* q_dq, void* stream) {
   CSMAE_REQUIRE(M > 0 && N > 0 && K > 0 && N % 4 == 0 && ldc % 4 == 0, "csmae_gemm_fp8: bad geometry M=%lld N=%lld K=%lld", M, N, K);
-  CSMAE_REQUIRE(A && B && (C || (q_out && c_dtype == CSMAE_BF16 && (epilogue == EPI_DGELU || epilogue == 6 || epilogue == 7 || epilogue == EPI_NONE))),
+  CSMAE_REQUIRE(A && B && (C || (q_out && c_dtype == CSMAE_BF16 && (epilogue == EPI_DGELU || epilogue == EPI_GELU_Q8 || epilogue == EPI_DGELU_Q8 || epilogue == EPI_NONE))),
                 "csmae_gemm_fp8: null operand (C may be null only with the fused fp8 copy and a non-residual epilogue: then that copy is the product's only output)");
   CSMAE_REQUIRE(a_fmt == 0 || a_fmt == 1, "csmae_gemm_fp8: a_fmt 0 (e4m3) or 1 (e5m2)");
-  const int q8 = (epilogue == 6 || epilogue == 7);
-  if (q8) epilogue = epilogue == 6 ? EPI_GELU : EPI_DGELU;
+  const int q8 = (epilogue == EPI_GELU_Q8 || epilogue == EPI_DGELU_Q8);
+  if (q8) epilogue = epilogue == EPI_GELU_Q8 ? EPI_GELU : EPI_DGELU;
   CSMAE_REQUIRE(!q8 || c_dtype == CSMAE_BF16, "csmae_gemm_fp8: the 8-bit gelu' epilogues write bf16");
   CSMAE_REQUIRE(epilogue >= EPI_NONE && epilogue <= EPI_DGELU, "csmae_gemm_fp8: epilogue %d", epilogue);
   CSMAE_REQUIRE(K % 16 == 0 && lda % 16 == 0 && ldb % 16 == 0 && (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "csmae_gemm_fp8: K, lda, ldb multiples of 16 bytes, 16-byte aligned operands");
@@ -996,10 +996,10 @@ static bool k2_wanted(int mode, int epilogue, long long K, long long N, long lon
 bool gemm_k2_nn_wanted(int epilogue, long long K, long long N, long long M) { return k2_wanted(g_k2_nn, epilogue, K, N, M); }
 bool gemm_k2_nt_wanted(int epilogue, long long K, long long N, long long M) { return k2_wanted(g_k2_nt, epilogue, K, N, M); }
 
-// The kernel gemm_core launches for a problem (csmae_gemm_route answers with it): GEMM_ROUTE_F32 for fp32 operands, else the bf16 tile
+// The kernel gemm_core launches for a problem (csmae_gemm_route answers with it): CSMAE_GEMM_ROUTE_F32 for fp32 operands, else the bf16 tile
 // configuration (0..6, as csmae_gemm_force_tile numbers them).  `epilogue` with the 8-bit gelu' forms already mapped to EPI_GELU / EPI_DGELU.
 static int gemm_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, int epilogue, int splitk) {
-  if (dtype != CSMAE_BF16) return GEMM_ROUTE_F32;
+  if (dtype != CSMAE_BF16) return CSMAE_GEMM_ROUTE_F32;
   // tile choice: as large as keeps >= ~1.5 rounds of the 256 CUs busy (bytes staged per flop ~ 1/BM + 1/BN)
   // tile choice (measured on the step's shapes, tools/gemm_bench.py): 256x256 wins whenever it fits, also when it leaves
   // fewer tiles than CUs (N = 768 outputs: 150 tiles) because it halves the bytes staged per flop; 256x128 never won.
@@ -1034,8 +1034,8 @@ int gemm_core(int dtype, int transA, int transB, long long M, long long N, long 
                      int splitk, void* stream) {
   CSMAE_REQUIRE(M > 0 && N > 0 && K > 0, "csmae_gemm: empty problem M=%lld N=%lld K=%lld", M, N, K);
   CSMAE_REQUIRE(N % 4 == 0 && ldc % 4 == 0, "csmae_gemm: N and ldc must be multiples of 4 (N=%lld ldc=%lld)", N, ldc);
-  const int q8 = (epilogue == 6 || epilogue == 7);   // CSMAE_EPI_GELU_Q8 / CSMAE_EPI_DGELU_Q8: gelu' as one byte per element
-  if (q8) epilogue = epilogue == 6 ? EPI_GELU : EPI_DGELU;
+  const int q8 = (epilogue == EPI_GELU_Q8 || epilogue == EPI_DGELU_Q8);   // gelu' as one byte per element
+  if (q8) epilogue = epilogue == EPI_GELU_Q8 ? EPI_GELU : EPI_DGELU;
   CSMAE_REQUIRE(!q8 || (dtype == CSMAE_BF16 && c_dtype == CSMAE_BF16), "csmae_gemm: the 8-bit gelu' epilogues belong to the bf16 path");
   CSMAE_REQUIRE(epilogue >= EPI_NONE && epilogue <= EPI_SPLIT, "csmae_gemm: bad epilogue %d", epilogue);
   CSMAE_REQUIRE((epilogue != EPI_ATOMIC && epilogue != EPI_SPLIT) || c_dtype == CSMAE_F32, "csmae_gemm: split-K accumulate needs fp32 C");
@@ -1119,7 +1119,7 @@ extern "C" int csmae_gemm(int dtype, int transA, int transB, long long M, long l
 // what csmae_gemm would launch (csmae_gemm_route; csmae_gemm_ks_route for its fallback): the epilogue as the caller passes it
 int gemm_core_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, int epilogue, int splitk) {
   if (dtype != CSMAE_F32 && dtype != CSMAE_BF16) return CSMAE_ERR_UNSUPPORTED;
-  return gemm_route(dtype, transA, transB, M, N, K, lda, ldb, epilogue == 6 ? EPI_GELU : (epilogue == 7 ? EPI_DGELU : epilogue), splitk);
+  return gemm_route(dtype, transA, transB, M, N, K, lda, ldb, epilogue == EPI_GELU_Q8 ? EPI_GELU : (epilogue == EPI_DGELU_Q8 ? EPI_DGELU : epilogue), splitk);
 }
 extern "C" int csmae_gemm_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, long long ldc,
                                 int epilogue, int splitk) {
@@ -1145,8 +1145,6 @@ __global__ __launch_bounds__(256) void dw_reduce_kernel(long long n4, int S, lon
       db[m] = a;
     }
 }
-extern int csmae_colsum_launch(int dtype, long long M, int N, const void* x, long long ld, float* out, void* stream);
-
 extern "C" int csmae_gemm_dw(int dtype, long long M, long long N, long long K, const void* dY, long long ldy, const void* X, long long ldx,
                              float* dW, float* db, float* workspace, long long ws_elems, void* stream);
 // Workspace of a grouped launch: [nsplit][tiles] dense 256 x 256 fp32 slabs, then [nsplit][tiles][256] column-sum partials (only

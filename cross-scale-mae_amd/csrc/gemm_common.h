@@ -29,12 +29,14 @@ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
-#define EPI_NONE 0    // C = acc + bias
-#define EPI_GELU 1    // x = acc + bias ; C = gelu(x) ; aux = gelu'(x)
-#define EPI_RESID 2   // C = acc + bias + resid (resid in C's dtype: the fp32 residual stream, or the bf16 one of throughput mode)
-#define EPI_DGELU 3   // C = acc * aux   (aux = gelu'(x) saved by the forward epilogue)
-#define EPI_ATOMIC 4  // C(fp32) += acc   (split-K, atomics)
-#define EPI_SPLIT 5   // C(fp32)[split] = acc  (split-K partial slabs, reduced by dw_reduce_kernel: deterministic, no atomics)
+// the epilogue codes of include/csmae.h under the short names the kernels use (the numbers live in the header only)
+constexpr int EPI_NONE = CSMAE_EPI_NONE;      // C = acc + bias
+constexpr int EPI_GELU = CSMAE_EPI_GELU;      // x = acc + bias ; C = gelu(x) ; aux = gelu'(x)
+constexpr int EPI_RESID = CSMAE_EPI_RESID;    // C = acc + bias + resid (resid in C's dtype: the fp32 residual stream, or the bf16 one of throughput mode)
+constexpr int EPI_DGELU = CSMAE_EPI_DGELU;    // C = acc * aux   (aux = gelu'(x) saved by the forward epilogue)
+constexpr int EPI_ATOMIC = CSMAE_EPI_ATOMIC;  // C(fp32) += acc   (split-K, atomics)
+constexpr int EPI_SPLIT = CSMAE_EPI_SPLIT;    // C(fp32)[split] = acc  (split-K partial slabs, reduced by dw_reduce_kernel: deterministic, no atomics)
+constexpr int EPI_GELU_Q8 = CSMAE_EPI_GELU_Q8, EPI_DGELU_Q8 = CSMAE_EPI_DGELU_Q8;   // GELU / DGELU with aux = gelu'(x) as one byte per element (GP_Q8 code below): the entry points fold them into GemmArgs::aux_q8
 
 struct GemmArgs {
   const void* A; const void* B; void* C; const float* bias; void* aux; const void* resid;   // resid has C's dtype
@@ -530,9 +532,8 @@ int gemm_force_cfg();                 // csmae_gemm_force_tile's value (-1 = heu
 bool gemm_k2_nn_wanted(int epilogue, long long K, long long N, long long M);   // policy of csmae_gemm_k2_mode (gemm.hip)
 bool gemm_k2_nt_wanted(int epilogue, long long K, long long N, long long M);
 int gemm_k2_launch_nn(const GemmArgs& p, hipStream_t st);
-// route codes (csmae_gemm_route / csmae_gemm_ks_route, include/csmae.h): the bf16 tile configurations 0..6 of gemm_core, and
-#define GEMM_ROUTE_F32 7     // the fp32 kernel (gemm_f32_kernel)
-#define GEMM_ROUTE_KSLAB 8   // csmae_gemm_ks on the K-slab weight mirror (gemm_bf16_k2_kernel<false>)
+// route codes (csmae_gemm_route / csmae_gemm_ks_route, include/csmae.h): the bf16 tile configurations 0..6 of gemm_core, CSMAE_GEMM_ROUTE_F32 for the
+// fp32 kernel (gemm_f32_kernel) and CSMAE_GEMM_ROUTE_KSLAB for csmae_gemm_ks on the K-slab weight mirror (gemm_bf16_k2_kernel<false>)
 int gemm_core_route(int dtype, int transA, int transB, long long M, long long N, long long K, long long lda, long long ldb, int epilogue, int splitk);   // gemm_bf16_k2_kernel<true> (gemm_k2.hip)
 int gemm_core(int dtype, int transA, int transB, long long M, long long N, long long K, const void* A, long long lda, const void* B, long long ldb,
               void* C, long long ldc, int c_dtype, const float* bias, int epilogue, void* aux, long long ldaux, const void* resid, long long ldr,

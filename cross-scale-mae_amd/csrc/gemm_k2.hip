@@ -263,14 +263,14 @@ int gemm_k2_launch_nn(const GemmArgs& p0, hipStream_t st) {
 // whether csmae_gemm_ks runs the K-slab kernel (true) or hands the product to csmae_gemm with the plain weight (csmae_gemm_ks_route asks the same)
 static bool ks_taken(int dtype, long long M, long long N, long long K, const void* A, long long lda, const void* Bk, long long slab_rows, const void* C, long long ldc,
                      int epilogue) {
-  const int epi_kind = epilogue == 6 ? EPI_GELU : (epilogue == 7 ? EPI_DGELU : epilogue);
+  const int epi_kind = epilogue == EPI_GELU_Q8 ? EPI_GELU : (epilogue == EPI_DGELU_Q8 ? EPI_DGELU : epilogue);
   return dtype == CSMAE_BF16 && Bk && gemm_k2_nt_wanted(epi_kind, K, N, M) && (gemm_force_cfg() < 0 || (gemm_force_cfg() & 7) == 6) && K >= 64 && K % 64 == 0 && M >= 128 && N >= 256 && N % 4 == 0 && ldc % 4 == 0 && ldc >= N &&
          lda % 8 == 0 && lda >= K && slab_rows >= N && slab_rows % 4 == 0 && (M + 128) * lda * 2 < 0xFFFFFFF0ll && (K / 32) * slab_rows * 64 < 0xFFFFFFF0ll &&
          (((uintptr_t)A | (uintptr_t)Bk | (uintptr_t)C) & 15) == 0;
 }
 extern "C" int csmae_gemm_ks_route(int dtype, long long M, long long N, long long K, const void* A, long long lda, const void* Bk, long long slab_rows,
                                    long long ldb_plain, const void* C, long long ldc, int epilogue) {
-  if (ks_taken(dtype, M, N, K, A, lda, Bk, slab_rows, C, ldc, epilogue)) return GEMM_ROUTE_KSLAB;
+  if (ks_taken(dtype, M, N, K, A, lda, Bk, slab_rows, C, ldc, epilogue)) return CSMAE_GEMM_ROUTE_KSLAB;
   return gemm_core_route(dtype, 0, 0, M, N, K, lda, ldb_plain, epilogue, 1);
 }
 extern "C" int csmae_gemm_ks(int dtype, long long M, long long N, long long K, const void* A, long long lda, const void* Bk, long long slab_rows,
@@ -280,8 +280,8 @@ extern "C" int csmae_gemm_ks(int dtype, long long M, long long N, long long K, c
     CSMAE_REQUIRE(B_plain != nullptr, "csmae_gemm_ks: shape not taken by the K-slab kernel and no plain weight given (M=%lld N=%lld K=%lld)", M, N, K);
     return gemm_core(dtype, 0, 0, M, N, K, A, lda, B_plain, ldb_plain, C, ldc, c_dtype, bias, epilogue, aux, ldaux, resid, ldr, 1, stream);
   }
-  const int q8 = (epilogue == 6 || epilogue == 7);
-  if (q8) epilogue = epilogue == 6 ? EPI_GELU : EPI_DGELU;
+  const int q8 = (epilogue == EPI_GELU_Q8 || epilogue == EPI_DGELU_Q8);
+  if (q8) epilogue = epilogue == EPI_GELU_Q8 ? EPI_GELU : EPI_DGELU;
   CSMAE_REQUIRE(!q8 || c_dtype == CSMAE_BF16, "csmae_gemm_ks: the 8-bit gelu' epilogues write bf16");
   CSMAE_REQUIRE(epilogue >= EPI_NONE && epilogue <= EPI_DGELU, "csmae_gemm_ks: bad epilogue %d", epilogue);
   CSMAE_REQUIRE(!(epilogue == EPI_GELU || epilogue == EPI_DGELU) || (aux && ldaux % 4 == 0), "csmae_gemm_ks: gelu epilogues need aux");

@@ -3,12 +3,9 @@
 #pragma once
 #include "common.h"
 
-#define LOSS_MSE 0
-#define LOSS_L2 1
-#define LOSS_MAE 2
-#define LOSS_L1 3
-#define LOSS_BCE 4
-#define LOSS_NONE 5  // no per-patch term (pure ssim / ms_ssim): the gradient is the ssim family's `extra` alone
+// the per-element loss kinds of include/csmae.h (enum csmae_loss) under the short names the kernels use
+constexpr int LOSS_MSE = CSMAE_LOSS_MSE, LOSS_L2 = CSMAE_LOSS_L2, LOSS_MAE = CSMAE_LOSS_MAE, LOSS_L1 = CSMAE_LOSS_L1, LOSS_BCE = CSMAE_LOSS_BCE;
+constexpr int LOSS_NONE = 5;  // no per-patch term (pure ssim / ms_ssim): the gradient is the ssim family's `extra` alone
 
 __device__ __forceinline__ float elem_loss(int kind, float pred, float t) {
   if (kind == LOSS_MSE || kind == LOSS_L2) { float d = pred - t; return d * d; }

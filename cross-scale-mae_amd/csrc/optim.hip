@@ -258,7 +258,6 @@ __global__ __launch_bounds__(256) void colsum_kernel(long long M, int N, const T
   if (ty == 0 && col < N)
     for (int k = 0; k < 4; ++k) unsafeAtomicAdd(out + col + k, red[0][tx][k] + red[1][tx][k] + red[2][tx][k] + red[3][tx][k]);
 }
-int csmae_colsum_launch(int dtype, long long M, int N, const void* x, long long ld, float* out, void* stream);
 extern "C" int csmae_colsum(int dtype, long long M, int N, const void* x, long long ld, float* out, void* stream) {
   return csmae_colsum_launch(dtype, M, N, x, ld, out, stream);
 }

@@ -1,7 +1,7 @@
 /* libcsmae_hip — C ABI of the MI355X (gfx950) Cross-Scale MAE pre-training hot path.
  *
  * The reference (aicip/Cross-Scale-MAE) is pure Python and has NO native/FFI boundary of its own
- * (SURVEY §8b): its "operators" are ATen/timm calls inside `models_mae/*.py` and `engine_pretrain.py`.
+ * (SURVEY §8b): its "operators" are ATen/timm calls inside the Python files of `models_mae/` and `engine_pretrain.py`.
  * Each entry point below therefore cites the reference expression it replaces (paths relative to the
  * reference root) rather than a pre-existing FFI symbol.  INTEGRATION.md shows the ctypes binding a
  * maintainer of the reference would add.
