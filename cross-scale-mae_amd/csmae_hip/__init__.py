@@ -27,7 +27,7 @@ SSIM_KINDS = {"ssim": ("none", 1, 1.0), "ms_ssim": ("none", 5, 1.0), "mse_ssim":
 _ADDED_WITHIN_ABI = ("csmae_attn_route", "csmae_attn_stream_mode", "csmae_probe_pool_fwd", "csmae_bn1d_fwd", "csmae_head_linear_fwd",
                      "csmae_head_linear_bwd", "csmae_softmax_ce", "csmae_lars_step", "csmae_probe_pool_bwd", "csmae_head_linear_dx", "csmae_soft_ce",
                      "csmae_mixup_target", "csmae_mixup_cutmix", "csmae_pos_embed_grad", "csmae_eval_u8", "csmae_l2_normalize", "csmae_knn_select",
-                     "csmae_knn_vote", "csmae_recon_eval", "csmae_recon_eval_workspace_floats")   # additions that left ABI_VERSION alone (see load())
+                     "csmae_knn_vote", "csmae_recon_eval", "csmae_recon_eval_workspace_floats", "csmae_recon_panel")   # additions that left ABI_VERSION alone (see load())
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSMAE_LIB_PATH") or os.path.join(_HERE, "libcsmae_hip.so")   # (override: A/B builds of tools/)
 
@@ -117,6 +117,7 @@ _SIGNATURES = {
     "csmae_knn_vote": [L, I, I, P, P, P, F, P, P, P, P, I, P],
     "csmae_recon_eval_workspace_floats": [L, I, I, P],
     "csmae_recon_eval": [I, L, I, I, I, P, P, L, L, P, P, P, P, P],
+    "csmae_recon_panel": [I, L, I, I, I, P, P, L, L, P, P, P, I, I, I, I, I, I, I, I, I, I, P, P],
     "csmae_stream_create_cu_mask": [I, P, P],
     "csmae_stream_destroy": [P],
 }

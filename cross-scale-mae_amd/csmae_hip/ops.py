@@ -813,4 +813,33 @@ def recon_eval(img, pred, mean, std, p, out=None, st=None, ws=None):
     return out
 
 
-__all__ = [n for n in dir() if not n.startswith("_")]
+# ---- reconstruction contact sheets (csrc/recon_panel.hip)
+def recon_panel(img, pred, mask, mean, std, p, panels=(0, 1, 2), gap=2, bands=None, out=None, st=None):
+    """out [N, S, W, 3] uint8, W = K S + (K - 1) gap: per image one RGB row of the K = len(panels) panels, `gap` white pixels between neighbours.
+    Panel codes: 0 X, 1 X (1 - m), 2 Y, 3 Y m, 4 X (1 - m) + Y m with X = img * std + mean, Y = the un-patchified pred * std + mean, m = mask of the
+    pixel's patch; a value v becomes the byte int(min(max(255 v, 0), 255)).  img, pred, mean, std: as recon_eval takes them.  mask: fp32 [N, L]
+    contiguous, 1 = removed.  bands: the channels shown as red, green, blue; None = (0, 1, 2), or (0, 0, 0) for C = 1.  The library refuses
+    S % p != 0, 1 > K > 5, a code outside [0, 4], a band outside [0, C), gap < 0 and any other dtype of pred before it launches anything."""
+    N, C, S, S2 = img.shape
+    p = int(p)
+    assert img.dtype == torch.float32 and img.is_contiguous() and S == S2 and p > 0
+    assert pred.dim() == 3 and pred.shape == (N, (S // p) ** 2, p * p * C) and pred.stride(2) == 1, (tuple(pred.shape), pred.stride(), S, p, C)
+    assert mask.dtype == torch.float32 and mask.shape == (N, (S // p) ** 2) and mask.is_contiguous(), (tuple(mask.shape), mask.dtype)
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == C and std.numel() == C and mean.is_contiguous() and std.is_contiguous()
+    codes = [int(c) for c in panels]
+    K, gap = len(codes), int(gap)
+    br, bg, bb = (int(b) for b in (bands if bands is not None else ((0, 0, 0) if C == 1 else (0, 1, 2))))
+    W = K * S + (K - 1) * gap
+    if out is None:
+        out = torch.empty(N, S, max(W, 0), 3, device=img.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.shape == (N, S, W, 3) and out.is_contiguous(), (tuple(out.shape), out.dtype, (N, S, W, 3))
+    codes = (codes + [0] * 5)[:max(K, 5)]
+    t = _begin()
+    check(load().csmae_recon_panel(_DT.get(pred.dtype, -1), N, C, S, p, _p(img), _p(pred), pred.stride(1), pred.stride(0), _p(mask), _p(mean), _p(std), br, bg, bb,
+                                   codes[0], codes[1], codes[2], codes[3], codes[4], K, gap, _p(out), _s(st)), "csmae_recon_panel")
+    if t:
+        t.end("recon_panel", 3.0 * W * S * N + (4.0 + pred.element_size()) * N * min(C, 3) * S * S)   # work: the bytes written + the shown planes of both operands
+    return out
+
+
+__all__ =[n for n in dir() if not n.startswith("_")]

@@ -11,6 +11,9 @@ clean and at noise 0.25".  Every image of a folder goes through every checkpoint
     build's own, the reference draws its evaluation noise unseeded.
   * Output: `<output_dir>/log.txt` gets one JSON line per model — model, n_images, num_runs_each, noise, random_crop and `<metric>_mean` /
     `<metric>_std` over the images; `<output_dir>/per_image.csv` one row per (model, image) with the metrics as columns.
+  * `--panel_dir DIR` also writes reconstruction contact sheets, `DIR/img_<i>.png` for every image (`--panel_every N`: every N-th): one row per
+    checkpoint, each row the `--panels` (default x xm y: original | masked input | reconstruction) of run 0, from the forward that is scored
+    (`csmae_recon_panel`); `log.txt` then gets one more line naming the directory and the count of sheets.
   * Multi-process launches (WORLD_SIZE > 1) raise.
 
     python main_recon_eval.py --chkpt_basedir ../Model_Saving --chkpt_dirs run_a run_b --data_dir /data/fmow-rgb/val --noise gaussian 0.25
@@ -25,6 +28,7 @@ import numpy as np
 import torch
 
 METRIC_CHOICES = ("mse", "mae", "l1", "l2", "ssim", "ssd", "sad")
+PANEL_CHOICES = ("x", "xm", "y", "ym", "xm_ym")   # util.viz.PANEL_CODES
 
 
 def get_args_parser():
@@ -43,6 +47,10 @@ def get_args_parser():
     p.add_argument("--num_workers", type=int, default=4, help="decoding worker processes")
     p.add_argument("--output_dir", type=str, default="./out_recon_eval")
     p.add_argument("--device", type=str, default="cuda:0")
+    p.add_argument("--panel_dir", type=str, default=None, help="write reconstruction contact sheets (one PNG per image, one row per checkpoint) here")
+    p.add_argument("--panel_every", type=int, default=None, help="a sheet for every N-th image (default: every image)")
+    p.add_argument("--panels", type=str, nargs="+", default=["x", "xm", "y"], choices=PANEL_CHOICES,
+                   help="panels of a row: original, masked input, reconstruction, reconstruction on the masked patches, pasted")
     return p
 
 
@@ -87,8 +95,10 @@ def main(args):
 
         def images(size):
             return viz.SyntheticEvalImages(args.synthetic_len, size, args.num_runs_each, channels=channels)
+    panel_dir = getattr(args, "panel_dir", None)
+    panel_kw = {} if panel_dir is None else dict(panel_dir=panel_dir, panel_every=getattr(args, "panel_every", None), panels=tuple(getattr(args, "panels", ("x", "xm", "y"))))
     mtrs = viz.run_eval(models, args.data_dir, comp_metrics=args.metrics, use_noise=use_noise, num_runs_each=args.num_runs_each, batch_size=args.batch_size,
-                        random_crop=args.random_crop, max_samples=args.max_samples, num_workers=args.num_workers, images=images)
+                        random_crop=args.random_crop, max_samples=args.max_samples, num_workers=args.num_workers, images=images, **panel_kw)
     Path(args.output_dir).mkdir(parents=True, exist_ok=True)
     names = list(mtrs)
     results = []
@@ -100,6 +110,11 @@ def main(args):
             print("* " + "  ".join(f"{k} {v:.6g}" if isinstance(v, float) else f"{k} {v}" for k, v in stats.items()))
             f.write(json.dumps(stats) + "\n")
             results.append(stats)
+        if panel_dir is not None:
+            every = max(int(panel_kw["panel_every"] or 1), 1)
+            n_images = len(mtrs[names[0]][next(iter(models))])
+            sheets = len(range(0, n_images, every)) * len({m.input_size for m in models.values()})
+            f.write(json.dumps(dict(panel_dir=panel_dir, panel_every=every, panels=list(panel_kw["panels"]), sheets=sheets)) + "\n")
     with open(os.path.join(args.output_dir, "per_image.csv"), mode="w", encoding="utf-8", newline="") as f:
         w = csv.writer(f)
         w.writerow(["model", "image"] + names)

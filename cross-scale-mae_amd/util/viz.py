@@ -3,11 +3,15 @@ array, one masked forward of a single image -> (original, masked input, reconstr
 reconstruction pasted into the visible patches).
 
 The model forward is the HIP path (`model(x, mask_ratio=, mask_seed=)`); everything else here is host-side array handling.
-The reference's matplotlib figures (`plot_image`, `plot_reconstruction`, `plot_metrics_comp`, util/viz.py:208-316,501-624) are plotting
-UI — SURVEY §2 row 19, out of scope — and are not rebuilt: `run_one_image` + `util.metrics.calc_metric` give the arrays and scores a
-figure would show.
 
-`run_eval` (reference util/viz.py:319-498) is rebuilt without its figures and as the batched GPU sweep its TODO asks for: every image of a
+The picture of the reference's `plot_reconstruction` (util/viz.py:231-316) — Original | Input (Masked) | Reconstruction, one row per model — is
+built without matplotlib, as a contact sheet whose bytes `csmae_recon_panel` writes on the device, for a whole batch, from the operands of the
+forward: `reconstruction_panels` here, the row stacking and the PNG writer (`stack_sheets`, `write_sheet`) too.  The function itself,
+`plot_reconstruction` with the reference's arguments, its path rule and its captions, is `util.recon_plot.plot_reconstruction`: this module keeps
+no `plot_reconstruction` and no `plot_image` (tests/test_host_cpu.py holds it to that).  `plot_image` and `plot_metrics_comp`
+(util/viz.py:208-229,501-624) are matplotlib UI — SURVEY §2 row 19, out of scope — and are still not rebuilt.
+
+`run_eval` (reference util/viz.py:319-498) is rebuilt as the batched GPU sweep its TODO asks for: every image of a
 folder, `num_runs_each` seeded masks (and crops) each, through several models -> `mtrs[metric][model_name]` = one score per image.  A batch
 costs one forward and one `csmae_recon_eval` (util.metrics.batch_metrics); nothing is read back before the sweep ends.  What differs from
 the reference, on purpose:
@@ -17,7 +21,8 @@ the reference, on purpose:
     draws it unseeded on the host, so its noisy scores are not repeatable; this seeding is this build's own;
   * the multi-scale variants draw ONE crop box per batch (it only enters the training loss, never the prediction that is scored);
   * the compared original is the fp32 input the model saw, un-normalised (the reference keeps a float64 copy);
-  * the plot arguments are accepted and ignored."""
+  * the reference's plot arguments are accepted and ignored; sheets are asked for with `panel_dir` / `panel_every` / `panels` instead, and come from
+    the forward that is scored (same seeds, same noise)."""
 import os
 import re
 from typing import Optional
@@ -201,13 +206,86 @@ def eval_batch(model, imgs, seeds, names, mean=None, std=None):
     return metrics.batch_metrics(imgs, pred, model.patch_size, names, mean, std)
 
 
+# ---- contact sheets (csrc/recon_panel.hip): the arrays of run_one_image, in its order, as panel names -> kernel codes, and the reference's titles
+PANEL_CODES = {"x": 0, "xm": 1, "y": 2, "ym": 3, "xm_ym": 4}
+PANEL_TITLES = {"x": "Original", "xm": "Input (Masked)", "y": "Reconstruction", "ym": "Reconstruction (Masked)", "xm_ym": "Reconstruction + Visible"}
+
+
+def sheet_width(S, n_panels, gap):
+    return n_panels * S + (n_panels - 1) * gap
+
+
+def panel_codes(panels):
+    """Panel names (or codes) -> the list of codes the kernel takes."""
+    names = [panels] if isinstance(panels, (str, int)) else list(panels)
+    try:
+        return [PANEL_CODES[n] if isinstance(n, str) else int(n) for n in names]
+    except KeyError as e:
+        raise ValueError(f"unknown panel {e.args[0]!r}: {', '.join(PANEL_CODES)}") from None
+
+
+def _model_device(model):
+    return torch.device(model.device) if getattr(model, "device", None) is not None else next(model.parameters()).device
+
+
+@torch.no_grad()
+def masked_forward(model, imgs, seeds):
+    """The forward of eval_batch: row j of `imgs` masked under seeds[j] -> (pred [n, L, p*p*C], mask [n, L]) on the device."""
+    noise, box = mask_draws(model, seeds, imgs.device)
+    out = model._run(imgs, getattr(model, "mask_ratio", 0.75), noise, box)
+    return out[1], out[2]
+
+
+@torch.no_grad()
+def reconstruction_panels(model, imgs, seeds, panels=("x", "xm", "y"), gap=2, bands=None, mean=None, std=None, pred=None, mask=None):
+    """Contact-sheet rows of a batch -> uint8 [n, S, W, 3] on the device, W = K S + (K - 1) gap: for every image its K = len(panels) panels side by
+    side, `gap` white pixels between them, each value as the byte the reference's plot_image shows (int(clip(255 v, 0, 255))).  One masked forward
+    of `imgs` (on the device, normalised; row j masked under seeds[j]) exactly as eval_batch makes it, then one `csmae_recon_panel`; with `pred` and
+    `mask` given (the forward already made, e.g. the one that was scored) no forward runs and `seeds` is not used.  bands: the channels shown as red,
+    green, blue (None: 0, 1, 2; one channel: 0, 0, 0) — what makes 4-band input viewable.  mean / std default to the plot statistics."""
+    from csmae_hip import ops
+    if pred is None or mask is None:
+        pred, mask = masked_forward(model, imgs, seeds)
+    C = imgs.shape[1]
+    c = np.arange(C) % len(image_mean)
+    mean, std = image_mean[c] if mean is None else mean, image_std[c] if std is None else std
+    imgs = imgs.float().contiguous()
+    return ops.recon_panel(imgs, pred, mask.float().contiguous(), metrics._channel_stats(mean, C, imgs.device), metrics._channel_stats(std, C, imgs.device),
+                           model.patch_size, panels=panel_codes(panels), gap=gap, bands=bands)
+
+
+def stack_sheets(rows, gap=2):
+    """uint8 [H_i, W_i, 3] arrays top to bottom, `gap` white rows between neighbours, narrower ones padded with white on the right."""
+    W = max(r.shape[1] for r in rows)
+    parts = []
+    for i, r in enumerate(rows):
+        if i and gap:
+            parts.append(np.full((gap, W, 3), 255, dtype=np.uint8))
+        parts.append(r if r.shape[1] == W else np.concatenate([r, np.full((r.shape[0], W - r.shape[1], 3), 255, dtype=np.uint8)], axis=1))
+    return np.ascontiguousarray(np.concatenate(parts, axis=0))
+
+
+def write_sheet(path, sheet, meta=None):
+    """`sheet` (uint8 [H, W, 3]) as a PNG at `path`; `meta` as JSON beside it (the same name, .json)."""
+    from PIL import Image
+    Image.fromarray(sheet, mode="RGB").save(path, format="PNG")
+    if meta is not None:
+        import json
+        with open(os.path.splitext(path)[0] + ".json", "w", encoding="utf-8") as f:
+            json.dump(meta, f)
+
+
 def run_eval(models, basedir, comp_metrics=None, use_noise=None, num_runs_each=5, batch_size=64, random_crop=False, max_samples=None,
-             random_walk=False, walk_seed=None, resample=None, num_workers=4, images=None, **kwargs):
+             random_walk=False, walk_seed=None, resample=None, num_workers=4, images=None, panel_dir=None, panel_every=None, panels=("x", "xm", "y"),
+             **kwargs):
     """Scores of every `<basedir>/**/*.jpg` under each model of the dict `models`: `mtrs[metric][model_name]` = a list with one float per image, the
     mean over `num_runs_each` runs (run r of image i: crop seed and mask seed seed_str_to_int(f"{i}-{r}")).  `comp_metrics`: a name or a list of
     names of util.metrics.batch_metrics; None = all of METRICS_DICT but ms_ssim, as in the reference.  `use_noise`: e.g. ("gaussian", 0.25).
     `images`: a callable img_size -> dataset of (image, seed) items in EvalImages' order, instead of the files (main_recon_eval.py's synthetic
-    images).  The reference's plot arguments (do_plot_metrics_comp, do_plot_image_comp, plot_every, title, ...) are accepted and ignored."""
+    images).  The reference's plot arguments (do_plot_metrics_comp, do_plot_image_comp, plot_every, title, ...) are accepted and ignored.
+    `panel_dir`: write a contact sheet `<panel_dir>/img_<i:06d>.png` for every image i with i % panel_every == 0 (None: every image) — one row of
+    `panels` per model, from run 0 of that image and from the very forward that is scored; models of different input_size go to separate sheets
+    `img_<i:06d>_s<size>.png`.  Only the written images' bytes are read back.  None: nothing is written, and nothing else changes."""
     if not isinstance(models, dict):
         models = {"model": models}
     if comp_metrics is not None:
@@ -219,15 +297,22 @@ def run_eval(models, basedir, comp_metrics=None, use_noise=None, num_runs_each=5
     paths = None if images is not None else list(glob_helper(f"{basedir}/**/*.jpg", max_samples=max_samples, random_walk=random_walk, walk_seed=walk_seed))
     scores = {name: {model_name: [] for model_name in models} for name in names}
     n_items = 0
-    for size in sorted({m.input_size for m in models.values()}):
+    sizes = sorted({m.input_size for m in models.values()})
+    if panel_dir is not None:
+        os.makedirs(panel_dir, exist_ok=True)
+        every, runs = max(int(panel_every or 1), 1), max(num_runs_each, 1)
+    for size in sizes:
         group = {k: m for k, m in models.items() if m.input_size == size}
         ds = images(size) if images is not None else EvalImages(paths, size, num_runs_each, random_crop=random_crop, resample=resample)
         n_items = len(ds)
         loader = torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=num_workers, pin_memory=True, drop_last=False)
         stats = {}
+        k0 = 0                       # the dataset index of the batch's first item: item k is run k % runs of image k // runs
         for imgs, seeds in loader:   # (the workers decode the next batches while the GPU runs this one)
             seeds = seeds.tolist()
             clean = {}
+            picked = [] if panel_dir is None else [j for j in range(len(seeds)) if (k0 + j) % runs == 0 and ((k0 + j) // runs) % every == 0]
+            sheets = []
             for model_name, model in group.items():
                 dev = torch.device(model.device) if model.device is not None else next(model.parameters()).device
                 if dev not in clean:
@@ -236,9 +321,20 @@ def run_eval(models, basedir, comp_metrics=None, use_noise=None, num_runs_each=5
                         C = imgs.shape[1]
                         c = np.arange(C) % len(image_mean)
                         stats[dev] = (torch.as_tensor(image_mean[c], dtype=torch.float32).to(dev), torch.as_tensor(image_std[c], dtype=torch.float32).to(dev))
-                got = eval_batch(model, clean[dev], seeds, names, *stats[dev])
+                if picked:           # score and draw from one forward: eval_batch's two steps, with the prediction and the mask kept for the sheets
+                    pred, mask = masked_forward(model, clean[dev], seeds)
+                    got = metrics.batch_metrics(clean[dev], pred, model.patch_size, names, *stats[dev])
+                    sheets.append(reconstruction_panels(model, clean[dev][picked], None, panels=panels, mean=stats[dev][0], std=stats[dev][1],
+                                                        pred=pred[picked], mask=mask[picked]))
+                else:
+                    got = eval_batch(model, clean[dev], seeds, names, *stats[dev])
                 for name in names:
                     scores[name][model_name].append(got[name])
+            for t, j in enumerate(picked):
+                i = (k0 + j) // runs
+                fname = f"img_{i:06d}.png" if len(sizes) == 1 else f"img_{i:06d}_s{size}.png"
+                write_sheet(os.path.join(panel_dir, fname), stack_sheets([s[t].cpu().numpy() for s in sheets]))
+            k0 += len(seeds)
     n_images = n_items // max(num_runs_each, 1)
     mtrs = {name: {} for name in names}
     for name in names:

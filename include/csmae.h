@@ -406,6 +406,21 @@ int csmae_recon_eval_workspace_floats(long long N, int C, int S, long long* floa
 int csmae_recon_eval(int pred_dtype, long long N, int C, int S, int p, const float* img, const void* pred, long long ldp, long long img_stride,
                      const float* mean, const float* std, float* part, float* out, void* stream);
 
+/* ---- reconstruction contact sheets of a batch (util/viz.py reconstruction_panels, plot_reconstruction, run_eval; added within ABI version 7,
+ * csrc/recon_panel.hip).  out: uint8 [N][S][W][3], W = n_panels S + (n_panels - 1) gap, dense: per image one RGB row of n_panels panels with gap
+ * white (255) pixels between neighbours.  img, pred (pred_dtype, ldp, img_stride), mean, std: as csmae_recon_eval takes them.  mask: fp32 [N][L],
+ * L = (S / p)^2, 1 = patch removed, 0 = kept.  With X = img * std + mean, Y = the un-patchified pred * std + mean and m = mask of the pixel's patch,
+ * panel k shows, by its code panel<k> (panel<k> with k >= n_panels is ignored):
+ *   0 x: X    1 xm: X (1 - m)    2 y: Y    3 ym: Y m    4 xm_ym: X (1 - m) + Y m
+ * of the channels band_r, band_g, band_b (each in [0, C); C = 1: 0, 0, 0), every value v as the byte (int) min(max(255 v, 0), 255), truncating;
+ * a NaN gives 0, +inf 255, -inf 0, and an operand a panel does not show is not read.  One launch, no atomics, no workspace; every byte of out is
+ * written exactly once (out need not be cleared, and needs no alignment); an image's bytes depend on that image alone (not on N, not on n).
+ * Refused before any launch: a null pointer, N <= 0, S % p != 0, ldp / img_stride too small, a pred_dtype other than fp32 / bf16, a band outside
+ * [0, C), n_panels outside [1, 5], a code outside [0, 4], gap < 0, a sheet of 2^31 bytes or more, more workgroups than the grid holds. */
+int csmae_recon_panel(int pred_dtype, long long N, int C, int S, int p, const float* img, const void* pred, long long ldp, long long img_stride,
+                      const float* mask, const float* mean, const float* std, int band_r, int band_g, int band_b, int panel0, int panel1, int panel2,
+                      int panel3, int panel4, int n_panels, int gap, unsigned char* out, void* stream);
+
 
 /* ---- a stream confined to a subset of the compute units (ABI version 5).  The reference overlaps DDP's bucket all-reduces and autograd's
  * weight-gradient work with the main chain on CUDA streams that share every SM (main_pretrain.py:417-421); on MI355X a GEMM workgroup owns a
