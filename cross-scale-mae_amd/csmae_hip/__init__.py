@@ -27,7 +27,8 @@ SSIM_KINDS = {"ssim": ("none", 1, 1.0), "ms_ssim": ("none", 5, 1.0), "mse_ssim":
 _ADDED_WITHIN_ABI = ("csmae_attn_route", "csmae_attn_stream_mode", "csmae_probe_pool_fwd", "csmae_bn1d_fwd", "csmae_head_linear_fwd",
                      "csmae_head_linear_bwd", "csmae_softmax_ce", "csmae_lars_step", "csmae_probe_pool_bwd", "csmae_head_linear_dx", "csmae_soft_ce",
                      "csmae_mixup_target", "csmae_mixup_cutmix", "csmae_pos_embed_grad", "csmae_eval_u8", "csmae_l2_normalize", "csmae_knn_select",
-                     "csmae_knn_vote", "csmae_recon_eval", "csmae_recon_eval_workspace_floats", "csmae_recon_panel")   # additions that left ABI_VERSION alone (see load())
+                     "csmae_knn_vote", "csmae_recon_eval", "csmae_recon_eval_workspace_floats", "csmae_recon_panel", "csmae_augment_u16",
+                     "csmae_eval_u16")   # additions that left ABI_VERSION alone (see load())
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSMAE_LIB_PATH") or os.path.join(_HERE, "libcsmae_hip.so")   # (override: A/B builds of tools/)
 
@@ -91,6 +92,8 @@ _SIGNATURES = {
     "csmae_loss_finalize": [L, I, P, P, F, P, F, P, F, P, I, P, P],
     "csmae_augment_u8": [L, I, I, I, I, P, P, P, P, P, P],
     "csmae_eval_u8": [L, I, I, I, I, P, P, P, P, P, P],
+    "csmae_augment_u16": [L, I, I, I, I, I, P, P, P, P, P, P, P],
+    "csmae_eval_u16": [L, I, I, I, I, I, P, P, P, P, P, P, P],
     "csmae_next_launch_event": [P],
     "csmae_flush_launch_event": [P],
     "csmae_adamw": [L, P, P, P, P, P, P, P, F, F, F, F, F, F, P, P, P, P, P],

@@ -592,6 +592,29 @@ def eval_u8(src, meta, mean, inv_std, dst, st=None):
     check(load().csmae_eval_u8(N, C, Hmax, Wmax, dst.shape[-1], _p(src), _p(meta), _p(mean), _p(inv_std), _p(dst), _s(st)), "csmae_eval_u8")
 
 
+def _u16_args(src, meta, band, mean, inv_std, dst):
+    """The argument list the two multispectral launchers share: src [N, Hmax, Wmax, Cin] uint16, meta [N, 8] int32, band [Cout] int32 ON THE HOST
+    (the library reads and checks it before the launch), mean / inv_std [Cout] fp32, dst [N, Cout, S, S] fp32."""
+    N, Hmax, Wmax, Cin = src.shape
+    Cout = band.numel()
+    assert src.dtype == torch.uint16 and src.is_contiguous() and meta.dtype == torch.int32 and meta.shape == (N, 8) and meta.is_contiguous()
+    assert band.dtype == torch.int32 and not band.is_cuda and band.is_contiguous(), "band is a host int32 tensor"
+    assert mean.dtype == inv_std.dtype == torch.float32 and mean.numel() == inv_std.numel() == Cout
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.shape[0] == N and dst.shape[1] == Cout and dst.shape[-1] == dst.shape[-2]
+    return N, Cin, Cout, Hmax, Wmax, dst.shape[-1], _p(src), _p(meta), band.data_ptr(), _p(mean), _p(inv_std), _p(dst)
+
+
+def augment_u16(src, meta, band, mean, inv_std, dst, st=None):
+    """The training transform of multispectral tiles (util/datasets.py:489-564): src [N, Hmax, Wmax, Cin] uint16 in raw units, meta [N, 8] int32
+    {H, W, i, j, h, w, hflip, vflip}, band [Cout] host int32 (source band of each output channel, bit 8 = masked), dst [N, Cout, S, S] fp32."""
+    check(load().csmae_augment_u16(*_u16_args(src, meta, band, mean, inv_std, dst), _s(st)), "csmae_augment_u16")
+
+
+def eval_u16(src, meta, band, mean, inv_std, dst, st=None):
+    """The eval transform of multispectral tiles: as augment_u16 with meta {H, W, Hr, Wr, top, left, 0, 0} (util.gpu_input.eval_transform_params)."""
+    check(load().csmae_eval_u16(*_u16_args(src, meta, band, mean, inv_std, dst), _s(st)), "csmae_eval_u16")
+
+
 def cast_bf16(src, dst, st=None):
     check(load().csmae_cast_f32_to_bf16(src.numel(), _p(src), _p(dst), _s(st)), "csmae_cast_f32_to_bf16")
 

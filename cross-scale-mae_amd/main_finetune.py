@@ -7,8 +7,10 @@ Differences:
   * `--drop_path` defaults to 0.0 (the reference: 0.1) and a value above 0 raises: drop-path is not implemented in the MI355X blocks;
   * `--dataset_type rgb` (the default) reads the fMoW-RGB CSVs `--train_path` / `--test_path`: the loader workers only decode, the
     training and the eval transform of `util/datasets.py` run on the device (`util/gpu_input.py`); `--dataset_type synthetic`
-    (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches generated on the device; the multi-band readers (Sentinel /
-    EuroSAT / ...) need rasterio / fiona and are not wired (selecting them raises); the augmentation flags (`--aa`, `--color_jitter`,
+    (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches generated on the device; `--dataset_type euro_sat` reads
+    lists of 13-band uint16 tiles (`path label` lines; `--masked_bands`, `--dropped_bands`; `util/ms_input.py`, the transform on the device) and sets
+    the model's channels to 13 - len(dropped_bands); the other multi-band readers (Sentinel / NAIP / ...) need rasterio / fiona and are not wired
+    (selecting them raises); the augmentation flags (`--aa`, `--color_jitter`,
     `--reprob`, ...) are parsed and unused, as the reference's fMoW-RGB dataset ignores them too;
   * `--model` defaults to `vit_base_patch16` (the reference's default `mae_vit_base` names no factory of `models_vit`);
     `--embed_dim / --depth / --num_heads` override a factory's geometry for small runs;
@@ -112,7 +114,7 @@ def get_args_parser():
                    help="map the pre-training model's keys to ViT keys (applied by itself when the checkpoint holds encoder_pos_embed)")
     # ---- additive flags of the MI355X build
     p.add_argument("--synthetic_len", type=int, default=64, help="iterations per epoch of the synthetic loader (a quarter of it for evaluation)")
-    p.add_argument("--input_channels", type=int, default=3, help="bands of the synthetic loader / model")
+    p.add_argument("--input_channels", type=int, default=None, help="bands of the synthetic loader / model (3 when not given; euro_sat: 13 - len(dropped_bands))")
     p.add_argument("--print_freq", type=int, default=20, help="iterations between two drains of the device-side losses")
     p.add_argument("--embed_dim", type=int, default=None)
     p.add_argument("--depth", type=int, default=None)

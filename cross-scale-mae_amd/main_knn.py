@@ -16,7 +16,9 @@ ground-sample distances.  It stands beside `main_linprobe.py` and takes its flag
     eval kernel (a smoke path for the driver, not a measurement).
   * Output per scale: one line on stdout and one JSON line in `<output_dir>/log.txt` with the keys scale, knn_k, knn_t, bank_size, n_queries,
     top1, top5 (per cent), extract_img_per_s (feature extraction of the queries), search_s (search + vote).
-  * Multi-process launches (WORLD_SIZE > 1) raise; the multi-band readers raise as in `util.downstream`.
+  * `--dataset_type euro_sat` reads lists of 13-band uint16 tiles (`util/ms_input.py`; `--masked_bands`, `--dropped_bands`): bank and queries go
+    through `csmae_eval_u16` exactly as the rgb ones go through `csmae_eval_u8`, the reduced query size per scale included.
+  * Multi-process launches (WORLD_SIZE > 1) raise; the other multi-band readers raise as in `util.downstream`.
 
     python main_knn.py --model vit_base_patch16 --finetune out/checkpoint-199.pth --transform_checkpoint_keys --dataset_type rgb \\
         --train_path train_62classes.csv --test_path val_62classes.csv --batch_size 256 --knn_scales 1.0 0.5 0.25 0.125
@@ -31,7 +33,7 @@ import numpy as np
 import torch
 
 from main_linprobe import load_pretrained
-from util.downstream import autocast, build_loaders, build_model, make_output_dir
+from util.downstream import autocast, build_loaders, build_model, make_output_dir, resolve_input_channels
 
 LOG_KEYS = ("scale", "knn_k", "knn_t", "bank_size", "n_queries", "top1", "top5", "extract_img_per_s", "search_s")
 
@@ -51,6 +53,8 @@ def get_args_parser():
     p.add_argument("--train_path", default="./train_64.csv", type=str, help="Train .csv path (the bank)")
     p.add_argument("--test_path", default="/data2/HDD_16TB/fmow-rgb-preproc/val_224.csvv", type=str, help="Test .csv path (the queries)")
     p.add_argument("--dataset_type", type=str, default="rgb", choices=["rgb", "sentinel", "euro_sat", "naip", "smart", "spacenetv1", "resisc45", "synthetic"])
+    p.add_argument("--masked_bands", default=None, nargs="+", type=int, help="euro_sat: bands overwritten with their mean")
+    p.add_argument("--dropped_bands", type=int, nargs="+", default=None, help="euro_sat: bands removed from the input")
     p.add_argument("--nb_classes", default=62, type=int, help="number of the classification types")
     p.add_argument("--output_dir", type=str, default=None)
     p.add_argument("--output_dir_base", type=str, default="./out")
@@ -65,7 +69,7 @@ def get_args_parser():
     p.add_argument("--knn_dtype", type=str, default="bf16", choices=["bf16", "fp32"], help="dtype of the normalised features the similarity GEMM reads")
     # ---- additive flags of the MI355X build, as main_linprobe.py
     p.add_argument("--synthetic_len", type=int, default=64, help="batches of the synthetic bank (a quarter of it for the queries)")
-    p.add_argument("--input_channels", type=int, default=3, help="bands of the synthetic loader / model")
+    p.add_argument("--input_channels", type=int, default=None, help="bands of the synthetic loader / model (3 when not given; euro_sat: 13 - len(dropped_bands))")
     p.add_argument("--embed_dim", type=int, default=None)
     p.add_argument("--depth", type=int, default=None)
     p.add_argument("--num_heads", type=int, default=None)
@@ -91,16 +95,17 @@ def bank_subset(n_train, bank_max, seed):
 
 def eval_loader(args, device, path, size, bank_max=None):
     """-> (loader, its number of images): `path` under the eval transform at `size`, through util.downstream.build_loaders (which gives the eval
-    loader of `test_path`).  `bank_max`: keep a seeded random subset of the images (rgb)."""
+    loader of `test_path`).  `bank_max`: keep a seeded random subset of the images (rgb, euro_sat)."""
     a = copy.copy(args)
     a.eval, a.test_path, a.input_size = True, path, size
     _, loader, n = build_loaders(a, device)
     subset = bank_subset(n, bank_max, args.seed)
     if subset is not None:
         from util.gpu_input import PrefetchLoader, collate_uint8
+        from util.ms_input import collate_uint16
         ds = torch.utils.data.Subset(loader.dataset, subset.tolist())
         raw = torch.utils.data.DataLoader(ds, sampler=torch.utils.data.SequentialSampler(ds), batch_size=args.batch_size, num_workers=args.num_workers,
-                                          pin_memory=False, drop_last=False, collate_fn=collate_uint8)
+                                          pin_memory=False, drop_last=False, collate_fn=collate_uint16 if args.dataset_type == "euro_sat" else collate_uint8)
         loader = PrefetchLoader(raw, loader.augment)
     return loader, n
 
@@ -149,13 +154,14 @@ def main(args):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     args.eval = False
+    resolve_input_channels(args)
     synthetic = args.dataset_type == "synthetic"
     keep = None
     if synthetic:
         loader_bank, loader_val, n_val = build_loaders(args, device)
         n_train = len(loader_bank) * args.batch_size
         keep = bank_subset(n_train, args.bank_max, args.seed)
-    elif args.dataset_type == "rgb":
+    elif args.dataset_type in ("rgb", "euro_sat"):
         loader_bank, n_train = eval_loader(args, device, args.train_path, args.input_size, args.bank_max)
     else:
         build_loaders(args, device)   # raises: the multi-band readers are not wired

@@ -6,8 +6,10 @@ names, types and defaults), its model factory call, LR scaling, probe head (Batc
 Differences:
   * `--dataset_type rgb` (the default) reads the fMoW-RGB CSVs `--train_path` / `--test_path`: the loader workers only decode, the
     training and the eval transform of `util/datasets.py` run on the device (`util/gpu_input.py`); `--dataset_type synthetic`
-    (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches with fixed labels generated on the device; the multi-band
-    readers (Sentinel / EuroSAT / ...) need rasterio / fiona and are not wired (selecting them raises);
+    (+ `--synthetic_len`, `--input_channels`) feeds fixed in-memory batches with fixed labels generated on the device; `--dataset_type euro_sat`
+    reads lists of 13-band uint16 tiles (`path label` lines; `--masked_bands`, `--dropped_bands`; `util/ms_input.py`, the transform on the device)
+    and sets the model's channels to 13 - len(dropped_bands); the other multi-band readers (Sentinel / NAIP / ...) need rasterio / fiona and are
+    not wired (selecting them raises);
   * `--model` defaults to `vit_base_patch16` (the reference's default `mae_vit_base` names no factory of `models_vit`);
     `--embed_dim / --depth / --num_heads` override a factory's geometry for small runs;
   * the per-iteration loss and the top-1 / top-5 hit counts stay on the device and are drained every `--print_freq` iterations; a
@@ -57,6 +59,8 @@ def get_args_parser():
     p.add_argument("--train_path", default="./train_64.csv", type=str, help="Train .csv path")
     p.add_argument("--test_path", default="/data2/HDD_16TB/fmow-rgb-preproc/val_224.csvv", type=str, help="Test .csv path")
     p.add_argument("--dataset_type", type=str, default="rgb", choices=["rgb", "sentinel", "euro_sat", "naip", "smart", "spacenetv1", "resisc45", "synthetic"])
+    p.add_argument("--masked_bands", default=None, nargs="+", type=int, help="euro_sat: bands overwritten with their mean")
+    p.add_argument("--dropped_bands", type=int, nargs="+", default=None, help="euro_sat: bands removed from the input")
     p.add_argument("--nb_classes", default=62, type=int, help="number of the classification types")
     p.add_argument("--output_dir", type=str, default=None)
     p.add_argument("--output_dir_base", type=str, default="./out")
@@ -69,7 +73,7 @@ def get_args_parser():
     p.add_argument("--num_workers", type=int, default=10, help="decoding worker processes of the rgb loader")
     # ---- additive flags of the MI355X build
     p.add_argument("--synthetic_len", type=int, default=64, help="iterations per epoch of the synthetic loader (a quarter of it for evaluation)")
-    p.add_argument("--input_channels", type=int, default=3, help="bands of the synthetic loader / model")
+    p.add_argument("--input_channels", type=int, default=None, help="bands of the synthetic loader / model (3 when not given; euro_sat: 13 - len(dropped_bands))")
     p.add_argument("--print_freq", type=int, default=20, help="iterations between two drains of the device-side loss / accuracy counters")
     p.add_argument("--embed_dim", type=int, default=None)
     p.add_argument("--depth", type=int, default=None)

@@ -5,8 +5,10 @@ identical names, types and defaults: main_pretrain.py:41-356), model factory cal
 
 Differences, all additive:
   * `--dataset_type synthetic` (+ `--synthetic_len`, `--input_channels`) feeds in-memory N(0,1) batches generated on the device —
-    the fMoW / EuroSAT / NAIP / COCO loaders of `util/datasets.py` need rasterio/fiona/torchvision and are outside the hot-path scope
-    (SURVEY.md §2 row 16); selecting them raises with that explanation;
+    `--dataset_type euro_sat` reads `--train_path` as a list of 13-band uint16 tiles (`path label` lines, util/datasets.py:489-564): the workers
+    read, `csmae_augment_u16` transforms on the device (`util/ms_input.py`; `--masked_bands`, `--dropped_bands`), and the model's
+    `input_channels` becomes 13 - len(dropped_bands); the NAIP / COCO loaders of `util/datasets.py` need rasterio/fiona/torchvision and are
+    outside the hot-path scope (SURVEY.md §2 row 16): selecting them raises with that explanation;
   * the model is wrapped in `csmae_hip.parallel.DataParallel` (flat-buffer RCCL all-reduce overlapped with backward) instead of DDP,
     and the optimizer is the fused HIP AdamW with torch.optim.AdamW's state layout;
   * W&B / TensorBoard and the matplotlib reconstruction plots at checkpoint epochs (:589-626) are not wired (observability / plotting
@@ -148,16 +150,30 @@ def main(args):
     torch.manual_seed(seed)
     np.random.seed(seed)
 
-    if args.dataset_type not in ("synthetic", "fmow_rgb"):
-        raise NotImplementedError(f"--dataset_type {args.dataset_type}: the reference's multi-band readers (util/datasets.py) depend on rasterio / fiona "
-                                  "and are outside the MI355X hot-path scope; use --dataset_type synthetic / fmow_rgb or pass your own "
+    if args.dataset_type not in ("synthetic", "fmow_rgb", "euro_sat"):
+        raise NotImplementedError(f"--dataset_type {args.dataset_type}: this reader of the reference (util/datasets.py) depends on rasterio / fiona "
+                                  "and is outside the MI355X hot-path scope; use --dataset_type synthetic / fmow_rgb / euro_sat or pass your own "
                                   "iterable of (samples, _) to engine_pretrain.train_one_epoch")
+    if args.dataset_type == "euro_sat":
+        from util.ms_input import eurosat_channels
+        args.input_channels = eurosat_channels(args)   # 13 - len(dropped_bands); a conflicting --input_channels raises
     channels = args.input_channels or 3
     if device.type == "cuda":
         torch.cuda.set_device(getattr(args, "gpu", 0) if args.distributed else torch.cuda.current_device())
         device = torch.device("cuda", torch.cuda.current_device())
     if args.dataset_type == "synthetic":
         data_loader_train = SyntheticLoader(args.batch_size, channels, args.input_size, args.synthetic_len, device, seed)
+    elif args.dataset_type == "euro_sat":
+        # EuroSAT tile list (util/datasets.py:489-564): the workers read uint16 tiles; band masking, normalisation, flips, the bicubic
+        # RandomResizedCrop and the band selection run in one HIP kernel behind the same pinned double-buffered staging
+        from util.ms_input import EuroSatDataset, eurosat_loader
+        dataset = EuroSatDataset(args.train_path)
+        if args.distributed:
+            sampler = torch.utils.data.DistributedSampler(dataset, num_replicas=misc.get_world_size(), rank=misc.get_rank(), shuffle=True)
+        else:
+            sampler = torch.utils.data.RandomSampler(dataset)
+        data_loader_train = eurosat_loader(dataset, sampler, True, args, device)
+        data_loader_train.sampler = sampler
     else:
         # fMoW-RGB CSV (util/datasets.py:161-206): the workers only decode; flips, normalisation and the bicubic RandomResizedCrop of
         # the reference's transform (util/datasets.py:120-136) run in one HIP kernel behind pinned double-buffered uint8 staging

@@ -36,16 +36,34 @@ class SyntheticLoader:
             yield self.samples, self.targets
 
 
+def resolve_input_channels(args):
+    """Settle `args.input_channels` before loaders and model are built: euro_sat has 13 - len(dropped_bands) bands (a flag that says otherwise
+    raises ValueError); every other type keeps the flag, 3 when it was not given."""
+    if args.dataset_type == "euro_sat":
+        from util.ms_input import eurosat_channels
+        args.input_channels = eurosat_channels(args)
+    elif getattr(args, "input_channels", None) is None:
+        args.input_channels = 3
+    return args.input_channels
+
+
 def build_loaders(args, device):
-    """-> (train loader or None under --eval, eval loader, number of eval images) for --dataset_type synthetic / rgb.  Any other type raises
-    NotImplementedError; a missing CSV raises the FileNotFoundError of its read."""
+    """-> (train loader or None under --eval, eval loader, number of eval images) for --dataset_type synthetic / rgb / euro_sat.  Any other type
+    raises NotImplementedError; a missing CSV or tile list raises the FileNotFoundError of its read."""
+    resolve_input_channels(args)
+    if args.dataset_type == "euro_sat":
+        # EuroSAT lists of `path label` lines (util/datasets.py:489-564): the workers read uint16 tiles, the transform runs on the device
+        from util.ms_input import build_eurosat_loader
+        loader_train = None if args.eval else build_eurosat_loader(args.train_path, True, args, device)
+        loader_val = build_eurosat_loader(args.test_path, False, args, device)
+        return loader_train, loader_val, len(loader_val.dataset)
     if args.dataset_type == "synthetic":
         loader_train = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, args.synthetic_len, device, args.seed)
         loader_val = SyntheticLoader(args.batch_size, args.input_channels, args.input_size, args.nb_classes, max(1, args.synthetic_len // 4), device, args.seed)
         return loader_train, loader_val, len(loader_val) * args.batch_size
     if args.dataset_type != "rgb":
-        raise NotImplementedError(f"--dataset_type {args.dataset_type}: the reference's multi-band readers (util/datasets.py) depend on rasterio / fiona "
-                                  "and are not wired here; use --dataset_type rgb / synthetic or drive train_one_epoch / evaluate with your own "
+        raise NotImplementedError(f"--dataset_type {args.dataset_type}: this reader of the reference (util/datasets.py) depends on rasterio / fiona "
+                                  "and is not wired here; use --dataset_type rgb / euro_sat / synthetic or drive train_one_epoch / evaluate with your own "
                                   "iterable of (samples, labels)")
     if args.input_channels != 3:
         raise ValueError(f"--dataset_type rgb decodes 3 bands: --input_channels {args.input_channels} does not fit")
@@ -87,7 +105,7 @@ class PendingLosses:
 def build_model(args, drop_path_rate=0.0):
     """The reference's factory call, with --embed_dim / --depth / --num_heads overriding the factory's geometry."""
     geometry = {k: getattr(args, k) for k in ("embed_dim", "depth", "num_heads") if getattr(args, k) is not None}
-    return models_vit.__dict__[args.model](patch_size=args.patch_size, img_size=args.input_size, in_chans=args.input_channels,
+    return models_vit.__dict__[args.model](patch_size=args.patch_size, img_size=args.input_size, in_chans=resolve_input_channels(args),
                                            num_classes=args.nb_classes, drop_path_rate=drop_path_rate, global_pool=args.global_pool, **geometry)
 
 

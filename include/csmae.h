@@ -298,6 +298,15 @@ int csmae_augment_u8(long long N, int C, int Hmax, int Wmax, int S, const unsign
  * H x W -> Hr x Wr resize.  The host (util/gpu_input.py eval_transform_params) computes meta and refuses sizes the kernel cannot hold. */
 int csmae_eval_u8(long long N, int C, int Hmax, int Wmax, int S, const unsigned char* src, const int* meta, const float* mean,
                   const float* inv_std, float* dst, void* stream);
+/* The same two transforms for multispectral tiles (util/datasets.py:489-564, Dataset_eurosat; added within ABI version 7, csrc/multispectral.hip):
+ * src [N, Hmax, Wmax, Cin] uint16 in raw units (no / 255), meta as for the u8 pair, dst [N, Cout, S, S] fp32, 1 <= Cout <= Cin <= 13 and
+ * Wmax * Cin <= 12288.  band [Cout] int32 is a HOST array, read and checked before the launch: output channel k is source band band[k] & 0xFF;
+ * with bit 8 set the band is masked (every source value counts as mean[k], so the channel is exactly 0).  A source band that no entry names is
+ * dropped and never read.  mean, inv_std [Cout] fp32 on the device, in raw units, already gathered to the output channels. */
+int csmae_augment_u16(long long N, int Cin, int Cout, int Hmax, int Wmax, int S, const unsigned short* src, const int* meta,
+                      const int* band, const float* mean, const float* inv_std, float* dst, void* stream);
+int csmae_eval_u16(long long N, int Cin, int Cout, int Hmax, int Wmax, int S, const unsigned short* src, const int* meta,
+                   const int* band, const float* mean, const float* inv_std, float* dst, void* stream);
 
 /* ---- optimizer side (main_pretrain.py:426-427 torch.optim.AdamW; util/misc.py:314 backward products) */
 /* gate (nullable device scalar): the update is skipped as a whole when it is not finite — engine_pretrain.py:56-58 raises on a
