@@ -5,6 +5,7 @@ Needs an MI355X."""
 import pytest
 import torch
 
+import attn_bwd_ref as BR
 import attn_stream_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -120,7 +121,8 @@ def run_guarded(ops, B, T, H, hd):
 def check_against_fp64(geom, out, lse, dqkv, what):
     B, T, H, hd = geom
     qkv_c, dout_c = R.inputs(B, T, H, hd)
-    ref, lse_ref, pabsv, grad = R.reference(qkv_c.cuda(), dout_c.cuda(), B, T, H, hd)
+    qkv, dout = qkv_c.cuda(), dout_c.cuda()
+    ref, lse_ref, pabsv, grad = R.reference(qkv, dout, B, T, H, hd)
     excess, ratio = R.fwd_excess(out, ref, pabsv)
     lse_err = float((lse.double() - lse_ref).abs().max())
     gscale = float(grad.abs().max())
@@ -132,6 +134,12 @@ def check_against_fp64(geom, out, lse, dqkv, what):
     assert excess <= 1.0, (what, geom, excess, ratio)
     assert lse_err <= 1e-3, (what, geom, lse_err)
     assert gworst <= 1.0, (what, geom, gworst)
+    # the per-element backward bounds of tests/attn_bwd_ref.py (both families round P, dS and the output to bf16 once: its "mfma" scheme):
+    # against the fp64 backward with the kernel's own out and lse, and against the autograd gradient
+    given, auto, line = BR.check_backward(qkv, dout, out, lse, dqkv, B, T, H, hd, "mfma", (ref, lse_ref, pabsv, grad))
+    print(f"{what} {geom}: {line}")
+    assert BR.worst(given) <= 1.0, (what, geom, given)
+    assert BR.worst(auto) <= 1.0, (what, geom, auto)
 
 
 # T one below, at and one above one and two streamed tiles (ATTN_STREAM_TILE = 64) and one and two owned blocks (ATTN_STREAM_OWN = 128:
