@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(int keep, int N, int 
 }
 extern "C" int csmae_patch_gather(int dtype, long long rows, int keep, int N, int C, int S, int p, const float* img0, const float* img1,
                                   const int* ids_keep, void* out, long long ld, void* stream) {
-  CSMAE_REQUIRE(rows > 0 && keep > 0 && N > 0 && S % p == 0 && ld >= (long long)C * p * p, "csmae_patch_gather: bad geometry");
+  CSMAE_REQUIRE(rows > 0 && keep > 0 && N > 0 && C > 0 && S > 0 && p > 0 && S % p == 0 && ld >= (long long)C * p * p, "csmae_patch_gather: bad geometry");
   CSMAE_REQUIRE(rows <= (long long)N * keep || img1, "csmae_patch_gather: second view requested but img1 is null");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == CSMAE_BF16) hipLaunchKernelGGL((patch_gather_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, keep, N, C, S, p, img0, img1, ids_keep, (bf16_t*)out, ld);
