@@ -22,13 +22,14 @@ ATTN_ROUTE_RESIDENT, ATTN_ROUTE_STREAM, ATTN_ROUTE_ANY, ATTN_ROUTE_F32 = 0, 1, 2
 ATTN_STREAM_OWN, ATTN_STREAM_TILE = 128, 64   # rows a streaming-attention workgroup owns / rows of one streamed tile (csrc/attention_common.h)
 LOSS_KINDS = {"mse": 0, "l2": 1, "mae": 2, "l1": 3, "bce": 4, "none": 5}
 # the ssim family: kind -> (per-patch kind, pyramid levels, weight of the ssim term)  MAE_ViT_Shared.py:165-267
+SEG_IGNORE = 255   # CSMAE_SEG_IGNORE: the label value csmae_seg_ce leaves out
 SSIM_KINDS = {"ssim": ("none", 1, 1.0), "ms_ssim": ("none", 5, 1.0), "mse_ssim": ("mse", 1, 0.1), "mse_ms_ssim": ("mse", 5, 0.1)}
 
 _ADDED_WITHIN_ABI = ("csmae_attn_route", "csmae_attn_stream_mode", "csmae_probe_pool_fwd", "csmae_bn1d_fwd", "csmae_head_linear_fwd",
                      "csmae_head_linear_bwd", "csmae_softmax_ce", "csmae_lars_step", "csmae_probe_pool_bwd", "csmae_head_linear_dx", "csmae_soft_ce",
                      "csmae_mixup_target", "csmae_mixup_cutmix", "csmae_pos_embed_grad", "csmae_eval_u8", "csmae_l2_normalize", "csmae_knn_select",
                      "csmae_knn_vote", "csmae_recon_eval", "csmae_recon_eval_workspace_floats", "csmae_recon_panel", "csmae_augment_u16",
-                     "csmae_eval_u16")   # additions that left ABI_VERSION alone (see load())
+                     "csmae_eval_u16", "csmae_seg_token_norm", "csmae_seg_ce", "csmae_seg_ce_bwd")   # additions that left ABI_VERSION alone (see load())
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSMAE_LIB_PATH") or os.path.join(_HERE, "libcsmae_hip.so")   # (override: A/B builds of tools/)
 
@@ -121,6 +122,9 @@ _SIGNATURES = {
     "csmae_recon_eval_workspace_floats": [L, I, I, P],
     "csmae_recon_eval": [I, L, I, I, I, P, P, L, L, P, P, P, P, P],
     "csmae_recon_panel": [I, L, I, I, I, P, P, L, L, P, P, P, I, I, I, I, I, I, I, I, I, I, P, P],
+    "csmae_seg_token_norm": [I, L, I, I, P, P, P, F, P, P],
+    "csmae_seg_ce": [L, I, I, I, I, P, P, P, P, P, P, P, P],
+    "csmae_seg_ce_bwd": [L, I, I, I, I, P, P, P, P, P, P],
     "csmae_stream_create_cu_mask": [I, P, P],
     "csmae_stream_destroy": [P],
 }

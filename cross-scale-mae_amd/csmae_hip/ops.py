@@ -865,4 +865,46 @@ def recon_panel(img, pred, mask, mean, std, p, panels=(0, 1, 2), gap=2, bands=No
     return out
 
 
+# ---- linear segmentation probe (csrc/segment.hip)
+SEG_CE_SCRATCH_FLOATS = 2048   # scratch floats of a csmae_seg_ce launch
+
+
+def seg_token_norm(x, gamma, beta, out, eps=1e-6, st=None):
+    """out [N L, D] fp32 = LayerNorm of the L patch tokens of x [N, L + 1, D] (fp32 or bf16, contiguous); the cls row of each image is dropped."""
+    N, T, D = x.shape
+    assert x.is_contiguous() and out.shape == (N * (T - 1), D) and gamma.numel() == D and beta.numel() == D
+    _f32c(gamma, beta, out)
+    check(load().csmae_seg_token_norm(dt(x), N, T, D, _p(x), _p(gamma), _p(beta), float(eps), _p(out), _s(st)), "csmae_seg_token_norm")
+    return out
+
+
+def seg_ce(pl, labels, loss, count, dpl=None, conf=None, scratch=None, gscale=None, pred=None, st=None):
+    """Mean cross-entropy of the patch logits pl [N, G, G, K] (fp32), upsampled bilinearly (align_corners=False) to the S x S labels [N, S, S] (uint8,
+    255 = ignored; None only with pred): loss [1] fp32, count [1] int64 = the valid pixels.  With no valid pixel the loss is 0 and the gradient all
+    zeros (torch.nn.functional.cross_entropy gives NaN there).  dpl [N, G, G, K] (optional) = gscale d loss / d pl (gscale: device scalar or None),
+    every element written.  conf [K, K] int64 (optional) += the confusion counts, rows = true class, columns = argmax class; the caller zeroes it.
+    pred [N, S, S] uint8 (optional) = the argmax class of every pixel.  The library refuses K outside [2, 64], S / G not in {4, 8, 14, 16} and
+    S != G (S / G) before it launches anything."""
+    N, G, G2, K = pl.shape
+    S = (labels if labels is not None else pred).shape[-1]
+    assert G == G2 and G > 0 and (labels is not None or pred is not None)
+    for t in (labels, pred):
+        assert t is None or (t.dtype == torch.uint8 and t.shape == (N, S, S) and t.is_contiguous()), "labels / pred: contiguous uint8 [N, S, S]"
+    assert loss.numel() >= 1 and count.dtype == torch.int64 and count.numel() >= 1 and count.is_contiguous()
+    assert dpl is None or (dpl.shape == pl.shape and labels is not None)
+    assert conf is None or (conf.dtype == torch.int64 and conf.shape == (K, K) and conf.is_contiguous())
+    _f32c(pl, loss, dpl, gscale)
+    if scratch is None:
+        scratch = torch.empty(SEG_CE_SCRATCH_FLOATS, device=pl.device, dtype=torch.float32)
+    _f32c(scratch)
+    assert scratch.numel() >= SEG_CE_SCRATCH_FLOATS
+    p = S // G
+    t = _begin()
+    check(load().csmae_seg_ce(N, G, p, K, S, _p(pl), _p(labels), _p(scratch), _p(loss), _p(count), _p(conf), _p(pred), _s(st)), "csmae_seg_ce")
+    if dpl is not None:
+        check(load().csmae_seg_ce_bwd(N, G, p, K, S, _p(pl), _p(labels), _p(count), _p(gscale), _p(dpl), _s(st)), "csmae_seg_ce_bwd")
+    if t:
+        t.end("seg_ce", float(N) * S * S + 4.0 * pl.numel() * (1 if dpl is None else 3))   # work: the label bytes + the logits (read again and written by the backward)
+
+
 __all__ =[n for n in dir() if not n.startswith("_")]

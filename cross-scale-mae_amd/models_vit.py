@@ -196,10 +196,8 @@ class VisionTransformer(nn.Module):
             raise AssertionError(f"input {tuple(x.shape)} does not match (N, {self.in_chans}, {self.img_size}, {self.img_size})")
         return x.contiguous().float()
 
-    def _features(self, x, training=False):
-        """feat [N, D] fp32 in a buffer of the model's (overwritten by the next call).  `training`: the trunk keeps its activations for one
-        Engine.backward_stream."""
-        from csmae_hip import ops
+    def _stream(self, x, training=False):
+        """The residual stream behind the last block, [N, L + 1, D] in the engine's workspace (fp32, or bf16 in throughput mode)."""
         x = self._check_input(x)
         eng = self._engine(x)
         N, L, D = x.shape[0], self.patch_embed.num_patches, self.embed_dim
@@ -207,7 +205,14 @@ class VisionTransformer(nn.Module):
         if ramp is None or ramp.shape != (N, L) or ramp.device != x.device:   # increasing noise: random_masking's argsort is the identity, nothing is dropped
             ramp = self._bufs["ramp"] = (torch.arange(L, dtype=torch.float32, device=x.device) / L).expand(N, L).contiguous()
         ws = eng.encode_stream(x, 0.0, ramp, training=training)
-        tokens = ws.enc["x"][len(self.blocks)].view(N, L + 1, D)   # the residual stream behind the last block: fp32, or bf16 in throughput mode
+        return ws.enc["x"][len(self.blocks)].view(N, L + 1, D)
+
+    def _features(self, x, training=False):
+        """feat [N, D] fp32 in a buffer of the model's (overwritten by the next call).  `training`: the trunk keeps its activations for one
+        Engine.backward_stream."""
+        from csmae_hip import ops
+        tokens = self._stream(x, training)
+        N, D = tokens.shape[0], self.embed_dim
         norm = self.fc_norm if self.global_pool else self.norm
         feat = self._buf("feat", (N, D))
         ops.probe_pool_fwd(tokens, norm.weight.detach(), norm.bias.detach(), feat, self.global_pool, eps=norm.eps)
@@ -297,6 +302,19 @@ class VisionTransformer(nn.Module):
     def forward_features(self, x):
         """[N, D]: pooled (global_pool) or cls-token features behind the final norm (models_vit.py:39-60).  Inference only."""
         return self._features(x).clone()
+
+    @torch.no_grad()
+    def forward_patch_tokens(self, x):
+        """[N, L, D] fp32: every patch token behind the final norm, the cls token dropped (dense features for main_segprobe.py).  Inference only.
+        `global_pool` plays no part: dense features take the model's `norm` (a model built with global_pool=True owns only `fc_norm`, which then
+        stands in)."""
+        from csmae_hip import ops
+        tokens = self._stream(x)
+        N, T, D = tokens.shape
+        norm = self.norm if hasattr(self, "norm") else self.fc_norm
+        out = torch.empty(N * (T - 1), D, device=tokens.device, dtype=torch.float32)
+        ops.seg_token_norm(tokens, norm.weight.detach(), norm.bias.detach(), out, eps=norm.eps)
+        return out.view(N, T - 1, D)
 
     def forward(self, x, target=None):
         """logits [N, K]; with `target`: (loss, logits).  Probe mode: int64 class indices, mean cross-entropy, differentiable w.r.t. the head.

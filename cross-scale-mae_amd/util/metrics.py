@@ -133,3 +133,26 @@ def f1_scores(y_true, y_pred, num_classes=None):
     macro = float(per_class.mean()) if per_class.size else 0.0
     micro = float(2.0 * tp.sum() / max(denom.sum(), 1.0))
     return macro, micro, per_class
+
+
+def miou_from_confusion(conf):
+    """-> (mIoU, per-class IoU [K] float64) of a confusion matrix [K, K] (rows = true class, columns = predicted class; a tensor or an array):
+    IoU_k = tp_k / (tp_k + fp_k + fn_k).  A class absent from both truth and prediction (an all-zero row and column) has no IoU: its entry is NaN
+    and it is left out of the mean (sklearn's jaccard_score would count it as 0).  With no class present the mean is 0."""
+    import numpy as np
+    cm = np.asarray(conf.detach().cpu() if torch.is_tensor(conf) else conf).astype(np.float64)
+    if cm.ndim != 2 or cm.shape[0] != cm.shape[1]:
+        raise ValueError(f"a confusion matrix is square, got {cm.shape}")
+    tp = np.diag(cm)
+    union = cm.sum(0) + cm.sum(1) - tp
+    present = union > 0
+    per_class = np.where(present, tp / np.maximum(union, 1.0), np.nan)
+    return (float(per_class[present].mean()) if present.any() else 0.0), per_class
+
+
+def pixel_accuracy_from_confusion(conf):
+    """The share of the counted pixels on the diagonal of a confusion matrix [K, K]; 0 for an empty matrix."""
+    import numpy as np
+    cm = np.asarray(conf.detach().cpu() if torch.is_tensor(conf) else conf).astype(np.float64)
+    total = cm.sum()
+    return float(np.trace(cm) / total) if total > 0 else 0.0

@@ -430,6 +430,34 @@ int csmae_recon_panel(int pred_dtype, long long N, int C, int S, int p, const fl
                       const float* mask, const float* mean, const float* std, int band_r, int band_g, int band_b, int panel0, int panel1, int panel2,
                       int panel3, int panel4, int n_panels, int gap, unsigned char* out, void* stream);
 
+/* ---- linear segmentation probe of the frozen encoder (main_segprobe.py, models_seg.py; added within ABI version 7, csrc/segment.hip).  The head itself
+ * is csmae_bn1d_fwd + csmae_head_linear_fwd / _bwd over the N L patch rows; these are the steps around it.  No floating-point atomics: two runs give
+ * the same loss and gradient bits. */
+/* The model's final LayerNorm on every PATCH token of the residual stream x [N, T = L + 1, D] (fp32 or bf16): the cls row of each image is dropped,
+ * out [N L, D] fp32, statistics in fp32 (mean, then centred squares).  One wave per token.  No backward: the trunk and its norm are frozen in a probe. */
+int csmae_seg_token_norm(int dtype, long long N, int T, int D, const void* x, const float* gamma, const float* beta, float eps, float* out,
+                         void* stream);
+/* Mean cross-entropy of bilinearly upsampled patch logits against per-pixel labels.  pl [N, G, G, K] fp32, labels [N, S, S] uint8 with S = G p; a
+ * label of CSMAE_SEG_IGNORE takes no part.  Interpolation rule: torch.nn.functional.interpolate(mode="bilinear", align_corners=False) — an output
+ * position i of an axis reads the source coordinate max((i + 0.5) / p - 0.5, 0), its integer part and the next cell clamped to G - 1, weighted by the
+ * fraction; the upsampled logits never reach memory.  Per valid pixel the stable log-softmax loss (maximum subtracted);
+ *   loss[0] = sum over valid pixels / count[0],  count[0] = the number of valid pixels.
+ * Empty-batch convention: with no valid pixel loss[0] = 0 and csmae_seg_ce_bwd writes zeros (torch's cross_entropy gives NaN there).
+ * conf (nullable) [K, K] int64, rows = true class, columns = argmax class (the lowest index wins ties), is ACCUMULATED into with integer atomics:
+ * the caller zeroes it, an evaluation sweep sums over its batches.  pred (nullable) [N, S, S] uint8 receives the argmax class of EVERY pixel, ignored
+ * ones too; labels may be NULL when pred is given (every pixel then counts as ignored).  Labels are the caller's contract: a value in [K, 255) is not
+ * detected — it names no class (its pixel contributes its log-sum-exp to the loss, its softmax to the gradient, nothing to conf); nothing is read
+ * or written out of bounds.  scratch: 2048 floats (per-workgroup partials, folded in a fixed order by a second launch).
+ * Refused before any launch: K outside [2, 64], p not in {4, 8, 14, 16}, G outside [1, 4096], S != G p, N S S >= 2^31, a null pointer. */
+#define CSMAE_SEG_IGNORE 255
+int csmae_seg_ce(long long N, int G, int p, int K, int S, const float* pl, const unsigned char* labels, float* scratch, float* loss, long long* count,
+                 long long* conf, unsigned char* pred, void* stream);
+/* dpl [N, G, G, K] = gscale / count[0] * sum over pixels of w(pixel, cell) (softmax - onehot), the gradient of loss[0] (gscale: nullable device scalar,
+ * 1 when absent; count: the device scalar csmae_seg_ce wrote — no host synchronisation).  A gather: each cell walks the at most 2 p x 2 p pixels
+ * that read it and recomputes their softmax from pl, so every element is written exactly once, in a fixed summation order: dpl need not be cleared. */
+int csmae_seg_ce_bwd(long long N, int G, int p, int K, int S, const float* pl, const unsigned char* labels, const long long* count, const float* gscale,
+                     float* dpl, void* stream);
+
 
 /* ---- a stream confined to a subset of the compute units (ABI version 5).  The reference overlaps DDP's bucket all-reduces and autograd's
  * weight-gradient work with the main chain on CUDA streams that share every SM (main_pretrain.py:417-421); on MI355X a GEMM workgroup owns a
