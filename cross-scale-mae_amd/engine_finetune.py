@@ -9,9 +9,7 @@ from typing import Iterable, Optional
 import numpy as np
 import torch
 
-import util.lr_sched as lr_sched
-import util.misc as misc
-from util.downstream import PendingLosses, autocast
+from util.downstream import autocast, train_epoch
 from util.metrics import f1_scores
 
 
@@ -19,34 +17,15 @@ def train_one_epoch(model: torch.nn.Module, criterion, data_loader: Iterable, op
                     loss_scaler, max_norm: float = 0, mixup_fn=None, log_writer=None, args=None, ignore_index=-9999):
     if args is None:
         raise Exception("args is None")
-    model.train(True)
-    metric_logger = misc.MetricLogger(delimiter="  ")
-    metric_logger.add_meter("lr", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
-    header = f"Epoch: [{epoch}]"
-    accum_iter, print_freq = args.accum_iter, getattr(args, "print_freq", 20)
-    optimizer.zero_grad()
-    n_iters = len(data_loader)
-    pending = PendingLosses()   # (with the largest group lr)
+    accum_iter = args.accum_iter
 
-    for it, (samples, targets) in enumerate(metric_logger.log_every(data_loader, print_freq, header)):
-        if it % accum_iter == 0:   # a per-iteration (not per-epoch) schedule
-            lr_sched.adjust_learning_rate(optimizer, it / n_iters + epoch, args)
-        samples, targets = samples.to(device, non_blocking=True), targets.to(device, non_blocking=True)
-        if mixup_fn is not None:
-            samples, targets = mixup_fn(samples, targets)
-        with autocast(device):
-            loss, _ = model(samples, targets)
-        pending.append(loss, max(g["lr"] for g in optimizer.param_groups))
-        loss_scaler(loss / accum_iter, optimizer, clip_grad=max_norm or None, parameters=model.parameters(), create_graph=False,
-                    update_grad=(it + 1) % accum_iter == 0)
-        if (it + 1) % accum_iter == 0:
+    def update(loss, it):   # the loss scaler runs backward, and clips and steps at the end of each accumulation window
+        last = (it + 1) % accum_iter == 0
+        loss_scaler(loss / accum_iter, optimizer, clip_grad=max_norm or None, parameters=model.parameters(), create_graph=False, update_grad=last)
+        if last:
             optimizer.zero_grad()
-        if it % print_freq == 0 or it == n_iters - 1:
-            pending.drain(metric_logger)   # exactly the iterations on which log_every prints the meters
-    pending.drain(metric_logger)
-    metric_logger.synchronize_between_processes()
-    print("Averaged stats:", metric_logger)
-    return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
+    optimizer.zero_grad()
+    return train_epoch(model, data_loader, optimizer, device, epoch, args, update, transform=mixup_fn)
 
 
 @torch.no_grad()

@@ -29,50 +29,28 @@ import json
 import os
 import time
 
-import numpy as np
 import torch
 
-from main_linprobe import load_pretrained
-from util.downstream import autocast, build_loaders, build_model, make_output_dir, resolve_input_channels
+from util.downstream import (add_checkpoint_flags, add_classification_data_flags, add_model_flags, add_pooling_flags, add_run_flags, autocast, build_loaders,
+                             build_model, load_pretrained, make_output_dir, resolve_input_channels, start_run)
 
 LOG_KEYS = ("scale", "knn_k", "knn_t", "bank_size", "n_queries", "top1", "top5", "extract_img_per_s", "search_s")
 
 
 def get_args_parser():
     p = argparse.ArgumentParser("Cross-MAE k-NN evaluation", add_help=False)
+    add_model_flags(p)
+    add_checkpoint_flags(p, "evaluate this pre-training checkpoint")
+    add_pooling_flags(p)
+    add_classification_data_flags(p)   # (--train_path is the bank, --test_path the queries)
+    add_run_flags(p)
     p.add_argument("--batch_size", default=512, type=int, help="images per feature-extraction batch")
-    p.add_argument("--model", default="vit_base_patch16", type=str, metavar="MODEL")
-    p.add_argument("--input_size", default=224, type=int)
-    p.add_argument("--patch_size", default=16, type=int)
-    p.add_argument("--finetune", default="", help="evaluate this pre-training checkpoint")
-    p.add_argument("--global_pool", action="store_true")
-    p.set_defaults(global_pool=False)
-    p.add_argument("--cls_token", action="store_false", dest="global_pool", help="Use class token instead of global pool for the features")
-    p.add_argument("--transform_checkpoint_keys", action="store_true", default=False,
-                   help="map the pre-training model's keys to ViT keys (applied by itself when the checkpoint holds encoder_pos_embed)")
-    p.add_argument("--train_path", default="./train_64.csv", type=str, help="Train .csv path (the bank)")
-    p.add_argument("--test_path", default="/data2/HDD_16TB/fmow-rgb-preproc/val_224.csvv", type=str, help="Test .csv path (the queries)")
-    p.add_argument("--dataset_type", type=str, default="rgb", choices=["rgb", "sentinel", "euro_sat", "naip", "smart", "spacenetv1", "resisc45", "synthetic"])
-    p.add_argument("--masked_bands", default=None, nargs="+", type=int, help="euro_sat: bands overwritten with their mean")
-    p.add_argument("--dropped_bands", type=int, nargs="+", default=None, help="euro_sat: bands removed from the input")
-    p.add_argument("--nb_classes", default=62, type=int, help="number of the classification types")
-    p.add_argument("--output_dir", type=str, default=None)
-    p.add_argument("--output_dir_base", type=str, default="./out")
-    p.add_argument("--device", type=str, default="cuda:0")
-    p.add_argument("--seed", default=0, type=int)
-    p.add_argument("--num_workers", type=int, default=10, help="decoding worker processes of the rgb loader")
     # ---- the k-NN protocol
     p.add_argument("--knn_k", type=int, default=20, help="neighbours that vote (1 .. 64)")
     p.add_argument("--knn_t", type=float, default=0.07, help="temperature of the vote weights exp(sim / T)")
     p.add_argument("--knn_scales", type=float, nargs="+", default=[1.0, 0.5, 0.25, 0.125], help="relative scales of the query images")
     p.add_argument("--bank_max", type=int, default=None, help="use a seeded random subset of this many training images as the bank")
     p.add_argument("--knn_dtype", type=str, default="bf16", choices=["bf16", "fp32"], help="dtype of the normalised features the similarity GEMM reads")
-    # ---- additive flags of the MI355X build, as main_linprobe.py
-    p.add_argument("--synthetic_len", type=int, default=64, help="batches of the synthetic bank (a quarter of it for the queries)")
-    p.add_argument("--input_channels", type=int, default=None, help="bands of the synthetic loader / model (3 when not given; euro_sat: 13 - len(dropped_bands))")
-    p.add_argument("--embed_dim", type=int, default=None)
-    p.add_argument("--depth", type=int, default=None)
-    p.add_argument("--num_heads", type=int, default=None)
     return p
 
 
@@ -142,17 +120,14 @@ def extract(model, loader, device, size_in=None, keep=None):
 
 
 def main(args):
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise NotImplementedError("multi-GPU k-NN evaluation is not implemented: run main_knn.py as one process (the bank and the search live on "
-                                  "one device; sharding the bank over ranks is not done by this script)")
-    if not 1 <= args.knn_k <= 64:
-        raise ValueError(f"--knn_k {args.knn_k}: the select kernel keeps 1 .. 64 neighbours")
-    sizes = [scaled_size(s, args.input_size) for s in args.knn_scales]
-    print(f"job dir: {os.path.dirname(os.path.realpath(__file__))}")
-    print(f"{args}".replace(", ", ",\n"))
-    device = torch.device(args.device)
-    torch.manual_seed(args.seed)
-    np.random.seed(args.seed)
+    sizes = []
+
+    def validate():
+        if not 1 <= args.knn_k <= 64:
+            raise ValueError(f"--knn_k {args.knn_k}: the select kernel keeps 1 .. 64 neighbours")
+        sizes.extend(scaled_size(s, args.input_size) for s in args.knn_scales)
+    device = start_run(args, "main_knn.py", "k-NN evaluation",
+                       "the bank and the search live on one device; sharding the bank over ranks is not done by this script", validate)
     args.eval = False
     resolve_input_channels(args)
     synthetic = args.dataset_type == "synthetic"

@@ -18,17 +18,14 @@ Multi-GPU probing is out of scope (WORLD_SIZE > 1 raises).
         --dataset_type folder --train_path data/train --test_path data/val --nb_classes 6 --batch_size 64 --epochs 20
 """
 import argparse
-import datetime
-import json
 import os
-import time
 
 import numpy as np
 import torch
 
-import util.lr_sched as lr_sched
 import util.misc as misc
-from util.downstream import PendingLosses, autocast, build_model, make_output_dir, nullable_string, scale_lr
+from util.downstream import (add_checkpoint_flags, add_model_flags, add_run_flags, add_schedule_flags, autocast, build_model, fit, lars_update,
+                             load_pretrained, make_output_dir, save_due, scale_lr, start_run, train_epoch)
 from util.lars import LARS
 from util.metrics import miou_from_confusion, pixel_accuracy_from_confusion
 
@@ -37,39 +34,14 @@ IGNORE = 255
 
 def get_args_parser():
     p = argparse.ArgumentParser("Cross-MAE Linear Segmentation Probe", add_help=False)
-    p.add_argument("--batch_size", default=64, type=int, help="Batch size per GPU (effective batch size is batch_size * accum_iter * # gpus")
-    p.add_argument("--epochs", default=50, type=int)
-    p.add_argument("--accum_iter", type=int, default=1)
-    p.add_argument("--model", default="vit_base_patch16", type=str, metavar="MODEL")
-    p.add_argument("--input_size", default=224, type=int)
-    p.add_argument("--patch_size", default=16, type=int)
-    p.add_argument("--weight_decay", type=float, default=0.0)
-    p.add_argument("--lr", type=float, default=None, metavar="LR")
-    p.add_argument("--blr", type=float, default=0.1, metavar="LR", help="base learning rate: absolute_lr = base_lr * total_batch_size / 256")
-    p.add_argument("--min_lr", type=float, default=0.0, metavar="LR")
-    p.add_argument("--warmup_epochs", type=int, default=0, metavar="N")
-    p.add_argument("--finetune", default="", help="probe from this pre-training checkpoint")
-    p.add_argument("--transform_checkpoint_keys", action="store_true", default=False,
-                   help="map the pre-training model's keys to ViT keys (applied by itself when the checkpoint holds encoder_pos_embed)")
+    add_schedule_flags(p, batch_size=64, warmup_epochs=0)
+    add_model_flags(p)
+    add_checkpoint_flags(p)
+    add_run_flags(p)
     p.add_argument("--train_path", default="./seg/train", type=str, help="folder: directory with images/ and masks/")
     p.add_argument("--test_path", default="./seg/val", type=str, help="folder: directory with images/ and masks/")
     p.add_argument("--dataset_type", type=str, default="folder", choices=["folder", "synthetic"])
     p.add_argument("--nb_classes", default=6, type=int, help="number of segmentation classes (2 .. 64)")
-    p.add_argument("--output_dir", type=str, default=None)
-    p.add_argument("--output_dir_base", type=str, default="./out")
-    p.add_argument("--device", type=str, default="cuda:0")
-    p.add_argument("--seed", default=0, type=int)
-    p.add_argument("--resume", type=nullable_string, default=None)
-    p.add_argument("--save_every", type=int, default=1)
-    p.add_argument("--start_epoch", default=0, type=int, metavar="N")
-    p.add_argument("--eval", action="store_true", help="Perform evaluation only")
-    p.add_argument("--num_workers", type=int, default=10, help="decoding worker processes of the folder loader")
-    # ---- additive flags of the MI355X build
-    p.add_argument("--synthetic_len", type=int, default=64, help="iterations per epoch of the synthetic loader (a quarter of it for evaluation)")
-    p.add_argument("--print_freq", type=int, default=20, help="iterations between two drains of the device-side losses")
-    p.add_argument("--embed_dim", type=int, default=None)
-    p.add_argument("--depth", type=int, default=None)
-    p.add_argument("--num_heads", type=int, default=None)
     return p
 
 
@@ -180,30 +152,7 @@ def build_seg_loaders(args, device):
 def train_one_epoch(model, data_loader, optimizer, device, epoch, args=None):
     """main_linprobe.py's epoch for the segmentation probe: LR schedule per iteration, gradient accumulation, losses drained every `print_freq`
     iterations; LARS skips on the device every update whose loss was not finite."""
-    model.train(True)
-    metric_logger = misc.MetricLogger(delimiter="  ")
-    metric_logger.add_meter("lr", misc.SmoothedValue(window_size=1, fmt="{value:.6f}"))
-    accum_iter, print_freq = args.accum_iter, getattr(args, "print_freq", 20)
-    optimizer.zero_grad(set_to_none=False)
-    n_iters = len(data_loader)
-    pending = PendingLosses()
-    gate = None
-    for it, (samples, labels) in enumerate(metric_logger.log_every(data_loader, print_freq, f"Epoch: [{epoch}]")):
-        if it % accum_iter == 0:
-            lr_sched.adjust_learning_rate(optimizer, it / n_iters + epoch, args)
-        with autocast(device):
-            loss, _ = model(samples, labels)
-        pending.append(loss, optimizer.param_groups[0]["lr"])
-        gate = loss.detach().reshape(1) if it % accum_iter == 0 else gate + loss.detach().reshape(1)
-        (loss / accum_iter).backward()
-        if (it + 1) % accum_iter == 0:
-            optimizer.step(gate=gate)
-            optimizer.zero_grad(set_to_none=False)
-        if it % print_freq == 0 or it == n_iters - 1:
-            pending.drain(metric_logger)
-    pending.drain(metric_logger)
-    print("Averaged stats:", metric_logger)
-    return {k: meter.global_avg for k, meter in metric_logger.meters.items()}
+    return train_epoch(model, data_loader, optimizer, device, epoch, args, lars_update(optimizer, args.accum_iter))
 
 
 @torch.no_grad()
@@ -228,16 +177,9 @@ def evaluate(data_loader, model, device, args=None):
 
 
 def main(args):
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise NotImplementedError("multi-GPU segmentation probing is not implemented: run main_segprobe.py as one process (the head is tiny; the "
-                                  "frozen trunk could be sharded over ranks, which this script does not do)")
-    from main_linprobe import load_pretrained
+    device = start_run(args, "main_segprobe.py", "segmentation probing",
+                       "the head is tiny; the frozen trunk could be sharded over ranks, which this script does not do")
     from models_seg import LinearSegProbe
-    print(f"job dir: {os.path.dirname(os.path.realpath(__file__))}")
-    print(f"{args}".replace(", ", ",\n"))
-    device = torch.device(args.device)
-    torch.manual_seed(args.seed)
-    np.random.seed(args.seed)
     if args.input_size % args.patch_size:
         raise ValueError(f"--input_size {args.input_size} is no multiple of --patch_size {args.patch_size}")
     loader_train, loader_val = build_seg_loaders(args, device)
@@ -261,21 +203,9 @@ def main(args):
     if args.eval:
         return evaluate(loader_val, model, device, args)
 
-    print(f"Start training for {args.epochs} epochs")
-    start_time = time.time()
-    best = 0.0
-    for epoch in range(args.start_epoch, args.epochs):
-        train_stats = train_one_epoch(model, loader_train, optimizer, device, epoch, args=args)
-        log_stats = {**{f"train_{k}": v for k, v in train_stats.items()}, "epoch": epoch}
-        if (epoch % args.save_every == 0 and epoch >= args.epochs / 2) or (epoch % 5 == 0 and epoch < args.epochs / 2) or epoch + 1 == args.epochs:
-            misc.save_model(args=args, model=model, model_without_ddp=model, optimizer=optimizer, loss_scaler=None, epoch=epoch)
-        test_stats = evaluate(loader_val, model, device, args)
-        best = max(best, test_stats["mIoU"])
-        print(f"Max mIoU: {best:.2f}%")
-        log_stats.update({f"test_{k}": v for k, v in test_stats.items()})
-        with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding="utf-8") as f:
-            f.write(json.dumps(log_stats) + "\n")
-    print(f"Training time {datetime.timedelta(seconds=int(time.time() - start_time))}")
+    fit(args, model, optimizer, None, log_name="log.txt", best=("mIoU", "Max mIoU"),
+        train=lambda epoch: train_one_epoch(model, loader_train, optimizer, device, epoch, args=args),
+        evaluate=lambda: evaluate(loader_val, model, device, args), save_at=lambda epoch: save_due(args, epoch, args.epochs / 2))
 
 
 if __name__ == "__main__":

@@ -2,11 +2,17 @@
 inside a larger allocation with sentinel padding on both sides (tests/seg_ref.py Guarded): after each launch the padding is intact, the inputs are
 unchanged, no output element is left unwritten, and every element is within the bound seg_ref derives for it (fp32 rounding of the stated formula,
 never a kernel's own output).  Each case prints its worst error / bound ratio (-s shows them).  Needs an MI355X."""
+import json
+import os
+import re
+import subprocess
+import sys
+
 import pytest
 import torch
 
 import seg_ref as R
-from finetune_ref import VIT_MICRO
+from finetune_ref import ROOT, VIT_MICRO, write_pretrain_checkpoint
 
 pytestmark = pytest.mark.gpu
 F32, BF, U8, I64 = torch.float32, torch.bfloat16, torch.uint8, torch.int64
@@ -282,3 +288,31 @@ def test_probe_prediction_and_evaluation(ops, e2e):
     assert float(ref["tie"].double().mean()) > 0 or torch.equal(conf.cpu(), 2 * ref["conf"])
     miou, per = miou_from_confusion(conf)
     assert 0.0 <= miou <= 1.0 and per.shape == (K_E2E,)
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def test_cli_synthetic_two_epochs_log_checkpoints_and_eval(ops, tmp_path):
+    """main_segprobe.main end to end in a child process: two epochs from the micro pre-training checkpoint, one log line and one checkpoint per
+    epoch, then --eval --resume of the last checkpoint, whose mIoU is the last epoch's (an integer confusion matrix over the same seeded batches)."""
+    ckpt = write_pretrain_checkpoint(tmp_path)
+    out = tmp_path / "out"
+    flags = ["--dataset_type", "synthetic", "--epochs", "2", "--save_every", "1", "--embed_dim", "128", "--depth", "2", "--num_heads", "2", "--input_size", "64",
+             "--patch_size", "16", "--batch_size", "4", "--nb_classes", "3", "--synthetic_len", "4", "--output_dir", str(out), "--device", "cuda"]
+    cwd = os.path.join(ROOT, "cross-scale-mae_amd")
+    run = subprocess.run([sys.executable, "main_segprobe.py", "--finetune", ckpt, "--transform_checkpoint_keys"] + flags, cwd=cwd, capture_output=True, text=True,
+                         timeout=300)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
+    lines = [json.loads(ln) for ln in open(out / "log.txt")]
+    assert [ln["epoch"] for ln in lines] == [0, 1]
+    for ln in lines:   # (memory_alloc / time_epoch / time_step are the meters log_every adds)
+        assert set(ln) == {"epoch", "train_loss", "train_lr", "train_memory_alloc", "train_time_epoch", "train_time_step", "test_loss", "test_mIoU", "test_pixel_acc", "test_iou"}, sorted(ln)
+    for epoch in (0, 1):
+        saved = torch.load(out / f"checkpoint-{epoch}.pth", map_location="cpu", weights_only=False)
+        assert {"model", "optimizer", "epoch"} <= set(saved) and saved["epoch"] == epoch
+    ev = subprocess.run([sys.executable, "main_segprobe.py", "--eval", "--resume", str(out / "checkpoint-1.pth")] + flags, cwd=cwd, capture_output=True, text=True,
+                        timeout=300)
+    assert ev.returncode == 0, ev.stdout[-2000:] + ev.stderr[-2000:]
+    found = re.search(r"^\* mIoU ([0-9.]+)", ev.stdout, flags=re.M)
+    assert found, ev.stdout[-1000:]
+    print(f"segprobe cli: test_mIoU {lines[-1]['test_mIoU']!r}, --eval prints {found.group(1)}")
+    assert found.group(1) == f"{lines[-1]['test_mIoU']:.3f}"
