@@ -3,7 +3,7 @@ PKG := cross-scale-mae_amd
 SRC := $(wildcard $(PKG)/csrc/*.hip)
 OBJ := $(patsubst $(PKG)/csrc/%.hip,build/obj/%.o,$(SRC))
 LIB := $(PKG)/csmae_hip/libcsmae_hip.so
-HDR := $(PKG)/csrc/common.h $(PKG)/csrc/gemm_common.h $(PKG)/csrc/attention_common.h $(PKG)/csrc/loss_common.h $(PKG)/csrc/ssim_common.h
+HDR := $(PKG)/csrc/common.h $(PKG)/csrc/gemm_common.h $(PKG)/csrc/attention_common.h $(PKG)/csrc/loss_common.h $(PKG)/csrc/ssim_common.h $(PKG)/csrc/seg_common.h
 HIPCC ?= hipcc
 HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result
 

@@ -29,7 +29,7 @@ _ADDED_WITHIN_ABI = ("csmae_attn_route", "csmae_attn_stream_mode", "csmae_probe_
                      "csmae_head_linear_bwd", "csmae_softmax_ce", "csmae_lars_step", "csmae_probe_pool_bwd", "csmae_head_linear_dx", "csmae_soft_ce",
                      "csmae_mixup_target", "csmae_mixup_cutmix", "csmae_pos_embed_grad", "csmae_eval_u8", "csmae_l2_normalize", "csmae_knn_select",
                      "csmae_knn_vote", "csmae_recon_eval", "csmae_recon_eval_workspace_floats", "csmae_recon_panel", "csmae_augment_u16",
-                     "csmae_eval_u16", "csmae_seg_token_norm", "csmae_seg_ce", "csmae_seg_ce_bwd")   # additions that left ABI_VERSION alone (see load())
+                     "csmae_eval_u16", "csmae_seg_token_norm", "csmae_seg_ce", "csmae_seg_ce_bwd", "csmae_segpanel")   # additions that left ABI_VERSION alone (see load())
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CSMAE_LIB_PATH") or os.path.join(_HERE, "libcsmae_hip.so")   # (override: A/B builds of tools/)
 
@@ -125,6 +125,7 @@ _SIGNATURES = {
     "csmae_seg_token_norm": [I, L, I, I, P, P, P, F, P, P],
     "csmae_seg_ce": [L, I, I, I, I, P, P, P, P, P, P, P, P],
     "csmae_seg_ce_bwd": [L, I, I, I, I, P, P, P, P, P, P],
+    "csmae_segpanel": [L, I, I, I, I, I, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, P, P, P],
     "csmae_stream_create_cu_mask": [I, P, P],
     "csmae_stream_destroy": [P],
 }

@@ -907,4 +907,44 @@ def seg_ce(pl, labels, loss, count, dpl=None, conf=None, scratch=None, gscale=No
         t.end("seg_ce", float(N) * S * S + 4.0 * pl.numel() * (1 if dpl is None else 3))   # work: the label bytes + the logits (read again and written by the backward)
 
 
+# ---- overlay sheets, argmax map and per-image counts of the segmentation probe (csrc/seg_panel.hip)
+def seg_panel(img, pl, labels, mean, std, palette, panes=(0, 3, 4), alpha=0.5, gap=2, bands=None, ignore_rgb=(224, 224, 192), out=None, pred=None, stats=None,
+              st=None):
+    """out [N, S, W, 3] uint8, W = P S + (P - 1) gap: per image one RGB row of the P = len(panes) panes, `gap` white pixels between neighbours.
+    Pane codes: 0 image, 1 gt, 2 pred, 3 gt_over, 4 pred_over, 5 errors (include/csmae.h states each byte).  img [N, C, S, S] fp32 contiguous,
+    normalised; mean, std fp32 [C]; pl [N, G, G, K] fp32 patch logits, S = G p, upsampled bilinearly as seg_ce does; labels uint8 [N, S, S] (255 =
+    ignored) or None; palette uint8 [K, 3] on the device; alpha: the overlay's weight, taken as a8 = round(256 alpha); bands: the channels shown as
+    red, green, blue (None = (0, 1, 2), or (0, 0, 0) for C = 1).  pred [N, S, S] uint8 (optional) = the argmax class of every pixel; stats [N, K, 3]
+    int32 (optional, needs labels) = per image and class (intersection, label area, prediction area), overwritten.  The library refuses K outside
+    [2, 64], S / G not in {4, 8, 14, 16}, S != G (S / G), 1 > P > 6, a code outside [0, 5], a pane 1, 3, 5 or stats without labels, a band outside
+    [0, C), gap < 0, alpha outside [0, 1] and N S W 3 >= 2^31 before it launches anything."""
+    N, C, S, S2 = img.shape
+    assert img.dtype == torch.float32 and img.is_contiguous() and S == S2
+    assert pl.dim() == 4 and pl.shape[0] == N and pl.shape[1] == pl.shape[2] and pl.shape[1] > 0, (tuple(pl.shape), N)
+    G, K = pl.shape[1], pl.shape[3]
+    _f32c(pl)
+    assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == C and std.numel() == C and mean.is_contiguous() and std.is_contiguous()
+    assert palette.dtype == torch.uint8 and palette.shape == (K, 3) and palette.is_contiguous(), (tuple(palette.shape), palette.dtype, K)
+    for t in (labels, pred):
+        assert t is None or (t.dtype == torch.uint8 and t.shape == (N, S, S) and t.is_contiguous()), "labels / pred: contiguous uint8 [N, S, S]"
+    assert stats is None or (stats.dtype == torch.int32 and stats.shape == (N, K, 3) and stats.is_contiguous()), "stats: contiguous int32 [N, K, 3]"
+    codes = [int(c) for c in panes]
+    P, gap = len(codes), int(gap)
+    br, bg, bb = (int(b) for b in (bands if bands is not None else ((0, 0, 0) if C == 1 else (0, 1, 2))))
+    ir, ig, ib = (int(v) for v in ignore_rgb)
+    a8 = int(round(256.0 * float(alpha)))
+    W = P * S + (P - 1) * gap
+    if out is None:
+        out = torch.empty(N, S, max(W, 0), 3, device=img.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.shape == (N, S, W, 3) and out.is_contiguous(), (tuple(out.shape), out.dtype, (N, S, W, 3))
+    codes = (codes + [0] * 6)[:max(P, 6)]
+    t = _begin()
+    check(load().csmae_segpanel(N, C, S, G, S // G, K, _p(img), _p(mean), _p(std), br, bg, bb, _p(pl), _p(labels), _p(palette), ir, ig, ib, a8, codes[0], codes[1],
+                                 codes[2], codes[3], codes[4], codes[5], P, gap, _p(out), _p(pred), _p(stats), _s(st)), "csmae_segpanel")
+    if t:
+        # work: the bytes written + the shown planes of the image + the labels + the logits
+        t.end("seg_panel", 3.0 * W * S * N + 4.0 * N * min(C, 3) * S * S + (0 if labels is None else N * S * S) + (0 if pred is None else N * S * S) + 4.0 * pl.numel())
+    return out
+
+
 __all__ =[n for n in dir() if not n.startswith("_")]

@@ -7,6 +7,7 @@
 //                    value, the valid count, the confusion matrix and the argmax map, without the upsampled logits ever reaching memory
 //   seg_ce_bwd       the gradient of that loss w.r.t. the patch logits, as a gather over each cell's footprint
 #include "common.h"
+#include "seg_common.h"   // SegAxis / seg_axis, SegPixel / seg_pixel: the bilinear upsampling of the patch logits, shared with seg_panel.hip
 
 // ---- LayerNorm of the patch tokens.  One wave per token, lanes across D; a workgroup is four waves.  Vector form: a lane holds up to SEG_LN_V4
 // groups of 4 consecutive columns in registers (one read of the row); scalar form (any D, any alignment): three passes over the row, the
@@ -80,35 +81,6 @@ extern "C" int csmae_seg_token_norm(int dtype, long long N, int T, int D, const 
   return csmae_check_launch("csmae_seg_token_norm");
 }
 
-// ---- bilinear upsampling of the patch logits, torch.nn.functional.interpolate(mode="bilinear", align_corners=False): output position i of an axis
-// reads source coordinate max((i + 0.5) / p - 0.5, 0) = max(2 i + 1 - p, 0) / (2 p) — formed in integers, so the cell index is exact and the
-// fraction takes one rounding; the second neighbour is clamped to G - 1.
-struct SegAxis { int i0, i1; float f; };
-__device__ __forceinline__ SegAxis seg_axis(int i, int p, int G) {
-  const int t = max(2 * i + 1 - p, 0), q = t / (2 * p);   // q <= G - 1 for i < G p
-  SegAxis a;
-  a.i0 = q;
-  a.i1 = min(q + 1, G - 1);
-  a.f = (float)(t - q * 2 * p) / (float)(2 * p);
-  return a;
-}
-// One pixel's view of the logits: the four neighbouring cells' rows and the weights of the two axes.  z(k) is the upsampled logit of class k, the
-// same expression wherever it is formed: hy0 (hx0 a + hx1 b) + hy1 (hx0 c + hx1 d).
-struct SegPixel {
-  const float *a, *b, *c, *d;
-  float hx0, hx1, hy0, hy1;
-  __device__ __forceinline__ float z(int k) const { return hy0 * (hx0 * a[k] + hx1 * b[k]) + hy1 * (hx0 * c[k] + hx1 * d[k]); }
-};
-__device__ __forceinline__ SegPixel seg_pixel(const float* __restrict__ pln /* the image's [G, G, K] logits */, int G, int K, const SegAxis& ay, const SegAxis& ax) {
-  SegPixel s;
-  s.a = pln + ((long long)ay.i0 * G + ax.i0) * K;
-  s.b = pln + ((long long)ay.i0 * G + ax.i1) * K;
-  s.c = pln + ((long long)ay.i1 * G + ax.i0) * K;
-  s.d = pln + ((long long)ay.i1 * G + ax.i1) * K;
-  s.hx1 = ax.f; s.hx0 = 1.f - ax.f;
-  s.hy1 = ay.f; s.hy0 = 1.f - ay.f;
-  return s;
-}
 // maximum m of the pixel's K logits, its first position, s = sum_k exp(z_k - m), and the label's logit (0 when the label names no class); two walks
 // over the classes, the logits formed twice from operands that sit in cache
 __device__ __forceinline__ void seg_softmax_stats(const SegPixel& px, int K, int label, float& m, int& arg, float& s, float& zl) {

@@ -6,6 +6,14 @@ upsamples bilinearly to the label resolution and scores against uint8 masks (`mo
 epoch the evaluation sweep accumulates one confusion matrix on the device; `mIoU`, `pixel_acc` and the per-class IoU are printed and appended
 to `<output_dir>/log.txt` as one JSON line.
 
+Looking at the predictions (all off by default; any of them makes the evaluation sweep call `csmae_segpanel` once per batch, on the patch logits it has
+just scored — util/seg_viz.py, csrc/seg_panel.hip; the printed lines and the returned numbers do not change, a later evaluation overwrites an earlier one):
+  * `--panel_dir DIR` writes an overlay sheet `DIR/<name>.png` per image (`--panel_every N`: every N-th): the `--panes` side by side (default
+    image gt_over pred_over; also gt, pred, errors), overlays blended with `--panel_alpha`;
+  * `--pred_dir DIR` writes the argmax map `DIR/<name>.png` per image, a palette PNG whose pixel values are the class indices;
+  * `--per_image` writes `<output_dir>/per_image.csv`: index, name, valid, pixel_acc, mIoU, iou_0 .. iou_{K-1} per image (an absent class: nan).
+  `<name>` is the image file's stem for `folder` and `img_<i:06d>` for `synthetic`.
+
 Data:
   * `--dataset_type synthetic` (+ `--synthetic_len`) needs no files: fixed in-memory batches whose label is a function of the patch's colour;
   * `--dataset_type folder --train_path DIR --test_path DIR`: DIR holds `images/*.png|jpg` and `masks/*.png` with equal stems; a mask is an 8-bit
@@ -30,6 +38,8 @@ from util.lars import LARS
 from util.metrics import miou_from_confusion, pixel_accuracy_from_confusion
 
 IGNORE = 255
+PANE_CHOICES = ("image", "gt", "pred", "gt_over", "pred_over", "errors")   # util.seg_viz.PANE_CODES
+DEFAULT_PANES = ("image", "gt_over", "pred_over")
 
 
 def get_args_parser():
@@ -42,6 +52,17 @@ def get_args_parser():
     p.add_argument("--test_path", default="./seg/val", type=str, help="folder: directory with images/ and masks/")
     p.add_argument("--dataset_type", type=str, default="folder", choices=["folder", "synthetic"])
     p.add_argument("--nb_classes", default=6, type=int, help="number of segmentation classes (2 .. 64)")
+    # the outputs of the evaluation sweep: absent from the namespace unless given (argparse.SUPPRESS), so a run without them parses, prints and does what it did
+    off = argparse.SUPPRESS
+    p.add_argument("--panel_dir", type=str, default=off, help="write an overlay sheet per evaluated image (one PNG, the --panes side by side) here")
+    p.add_argument("--panel_every", type=int, default=off, help="a sheet for every N-th image (default: every image)")
+    p.add_argument("--panes", type=str, nargs="+", default=off, choices=PANE_CHOICES,
+                   help="panes of a sheet: the image, the labels / the prediction as flat colours, each over the image, the wrong pixels in red "
+                        "(default: image gt_over pred_over)")
+    p.add_argument("--panel_alpha", type=float, default=off, help="weight of the colour in the overlay panes, 0 .. 1 (default 0.5)")
+    p.add_argument("--pred_dir", type=str, default=off, help="write the predicted class map of every evaluated image (a palette PNG of class indices) here")
+    p.add_argument("--per_image", action="store_true", default=off,
+                   help="write <output_dir>/per_image.csv: valid pixels, pixel accuracy, mIoU and per-class IoU of every image")
     return p
 
 
@@ -67,6 +88,9 @@ class SyntheticSegLoader:
     def __iter__(self):
         for _ in range(self.length):
             yield self.samples, self.targets
+
+    def image_name(self, i):
+        return f"img_{i:06d}"
 
 
 class SegFolderDataset(torch.utils.data.Dataset):
@@ -134,6 +158,14 @@ class SegFolderLoader:
     def __len__(self):
         return len(self.raw)
 
+    def image_name(self, i):
+        """The stem of the i-th image the loader yields (the eval loader is sequential: dataset order)."""
+        return os.path.splitext(os.path.basename(self.dataset.pairs[i][0]))[0]
+
+    def display_stats(self):
+        """(mean, std) that turn a normalised sample back into [0, 1] values: the transform's own"""
+        return self.augment.mean, 1.0 / self.augment.inv_std
+
     def __iter__(self):
         for images, masks in self.raw:
             labels = torch.stack([label_eval_transform(m, self.S) for m in masks])
@@ -155,18 +187,94 @@ def train_one_epoch(model, data_loader, optimizer, device, epoch, args=None):
     return train_epoch(model, data_loader, optimizer, device, epoch, args, lars_update(optimizer, args.accum_iter))
 
 
+def wants_outputs(args):
+    """True when a flag asks the evaluation sweep for more than its numbers (--panel_dir, --pred_dir, --per_image)."""
+    return args is not None and bool(getattr(args, "panel_dir", None) or getattr(args, "pred_dir", None) or getattr(args, "per_image", False))
+
+
+class SegOutputs:
+    """The files of one evaluation sweep.  `batch` enqueues one csmae_segpanel on the patch logits the batch was scored with and reads back only
+    what is written: the picked images' sheets, the class maps when --pred_dir is set; the counts stay on the device until `finish`."""
+
+    def __init__(self, args, data_loader, K, device):
+        from util.seg_viz import IGNORE_RGB, default_palette, device_palette, pane_codes
+        self.panel_dir, self.pred_dir, self.per_image = getattr(args, "panel_dir", None), getattr(args, "pred_dir", None), bool(getattr(args, "per_image", False))
+        self.every = max(int(getattr(args, "panel_every", None) or 1), 1)
+        self.alpha = float(getattr(args, "panel_alpha", 0.5))
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError(f"--panel_alpha {self.alpha}: a weight in [0, 1]")
+        # without sheets the kernel still writes one: the cheapest, a single flat pane
+        self.codes, self.gap = (pane_codes(getattr(args, "panes", DEFAULT_PANES)), 2) if self.panel_dir else ([2], 0)
+        self.K, self.device, self.loader, self.ignore_rgb = K, device, data_loader, IGNORE_RGB
+        self.palette_host = default_palette(K)
+        self.palette = device_palette(self.palette_host, K, device)
+        self.mean, self.std = data_loader.display_stats() if hasattr(data_loader, "display_stats") else (None, None)
+        if self.per_image and not getattr(args, "output_dir", None):
+            raise ValueError("--per_image writes <output_dir>/per_image.csv: no output_dir is set")
+        self.csv = os.path.join(args.output_dir, "per_image.csv") if self.per_image else None
+        for d in (self.panel_dir, self.pred_dir, args.output_dir if self.csv else None):
+            if d:
+                os.makedirs(d, exist_ok=True)
+        self.index, self.names, self.stats = 0, [], []
+
+    def batch(self, model, samples, labels, pl):
+        from util.seg_viz import segmentation_panels, write_mask_png
+        from util.viz import write_sheet
+        n, S = samples.shape[0], samples.shape[-1]
+        pred = torch.empty(n, S, S, device=samples.device, dtype=torch.uint8) if self.pred_dir else None
+        stats = torch.empty(n, self.K, 3, device=samples.device, dtype=torch.int32) if self.per_image else None
+        sheets = segmentation_panels(model, samples, labels, panes=self.codes, alpha=self.alpha, palette=self.palette, mean=self.mean, std=self.std,
+                                     patch_logits=pl, gap=self.gap, ignore_rgb=self.ignore_rgb, pred=pred, stats=stats)
+        names = [self.loader.image_name(self.index + j) if hasattr(self.loader, "image_name") else f"img_{self.index + j:06d}" for j in range(n)]
+        if self.panel_dir:
+            picked = [j for j in range(n) if (self.index + j) % self.every == 0]
+            if picked:
+                host = sheets[picked].cpu().numpy()
+                for t, j in enumerate(picked):
+                    write_sheet(os.path.join(self.panel_dir, names[j] + ".png"), host[t])
+        if pred is not None:
+            host = pred.cpu().numpy()
+            for j in range(n):
+                write_mask_png(os.path.join(self.pred_dir, names[j] + ".png"), host[j], self.palette_host)
+        if stats is not None:
+            self.stats.append(stats)
+        self.names += names
+        self.index += n
+
+    def finish(self):
+        if self.csv is None:
+            return
+        import csv
+
+        from util.metrics import per_image_scores
+        sc = per_image_scores(torch.cat(self.stats)) if self.stats else None
+        with open(self.csv, mode="w", encoding="utf-8", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["index", "name", "valid", "pixel_acc", "mIoU"] + [f"iou_{k}" for k in range(self.K)])
+            for i, name in enumerate(self.names):
+                w.writerow([i, name, int(sc["valid"][i]), repr(float(sc["pixel_acc"][i])), repr(float(sc["mIoU"][i]))] + [repr(float(v)) for v in sc["iou"][i]])
+
+
 @torch.no_grad()
 def evaluate(data_loader, model, device, args=None):
-    """-> {"loss", "mIoU", "pixel_acc", "iou"} over the loader in eval mode: one confusion matrix accumulated on the device, one host read at the end."""
+    """-> {"loss", "mIoU", "pixel_acc", "iou"} over the loader in eval mode: one confusion matrix accumulated on the device, one host read at the end.
+    With --panel_dir, --pred_dir or --per_image (SegOutputs) every batch's logits also go through csmae_segpanel; the numbers are the same."""
     model.eval()
     K = model.num_classes
     conf = torch.zeros(K, K, device=device, dtype=torch.int64)
+    outputs = SegOutputs(args, data_loader, K, device) if wants_outputs(args) else None
     sums, counts = [], []
     for samples, labels in data_loader:
         with autocast(device):
-            loss, count = model.evaluate_batch(samples, labels, conf)
+            if outputs is None:
+                loss, count = model.evaluate_batch(samples, labels, conf)
+            else:
+                loss, count, pl = model.evaluate_batch(samples, labels, conf, want_logits=True)
+                outputs.batch(model, samples, labels, pl)
         sums.append(loss.double() * count[0])
         counts.append(count[0])
+    if outputs is not None:
+        outputs.finish()
     total = int(torch.stack(counts).sum())
     miou, per_class = miou_from_confusion(conf)
     stats = {"loss": float(torch.stack(sums).sum()) / max(total, 1), "mIoU": 100.0 * miou, "pixel_acc": 100.0 * pixel_accuracy_from_confusion(conf),

@@ -130,8 +130,11 @@ class LinearSegProbe(nn.Module):
         return loss, pl
 
     @torch.no_grad()
-    def evaluate_batch(self, x, labels, conf):
+    def evaluate_batch(self, x, labels, conf, want_logits=False):
         """Adds the batch's confusion counts (rows = true class, columns = predicted class; ignored pixels skipped) into conf [K, K] int64 on the
-        device and returns (loss, valid-pixel count [1] int64), both on the device.  Call in eval mode: the running statistics normalise."""
-        loss, _, _, _ = self._pass(x, labels, want_grad=False, conf=conf)
+        device and returns (loss, valid-pixel count [1] int64), both on the device; with want_logits also, as a third value, the patch logits
+        [N, G, G, K] of this very forward (what csmae_segpanel draws and counts from).  Call in eval mode: the running statistics normalise."""
+        loss, pl, _, _ = self._pass(x, labels, want_grad=False, conf=conf)
+        if want_logits:
+            return loss, self.last_count, pl
         return loss, self.last_count

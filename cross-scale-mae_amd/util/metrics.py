@@ -156,3 +156,23 @@ def pixel_accuracy_from_confusion(conf):
     cm = np.asarray(conf.detach().cpu() if torch.is_tensor(conf) else conf).astype(np.float64)
     total = cm.sum()
     return float(np.trace(cm) / total) if total > 0 else 0.0
+
+
+def per_image_scores(stats):
+    """Per-image scores from the counts `csmae_segpanel` gathers: stats [N, K, 3] (a tensor or an array) of (intersection, label area, prediction
+    area) per image and class, counted over the image's valid pixels.  -> dict of numpy arrays: valid [N] int64 (the valid pixels = the sum of the
+    label areas), pixel_acc [N] (the intersections / valid; NaN for an image without a valid pixel), iou [N, K] = intersection / (label area +
+    prediction area - intersection), NaN for a class the image neither holds nor predicts, and mIoU [N] over the classes with
+    label area + prediction area > 0 (NaN where there is none) — miou_from_confusion's rule, image by image."""
+    import numpy as np
+    s = np.asarray(stats.detach().cpu() if torch.is_tensor(stats) else stats).astype(np.float64)
+    if s.ndim != 3 or s.shape[2] != 3:
+        raise ValueError(f"stats are [N, K, 3] (intersection, label area, prediction area), got {s.shape}")
+    inter, area_l, area_p = s[..., 0], s[..., 1], s[..., 2]
+    valid = area_l.sum(1)
+    present = (area_l + area_p) > 0
+    iou = np.where(present, inter / np.maximum(area_l + area_p - inter, 1.0), np.nan)
+    n_present = present.sum(1)
+    miou = np.where(n_present > 0, np.where(present, iou, 0.0).sum(1) / np.maximum(n_present, 1), np.nan)
+    acc = np.where(valid > 0, inter.sum(1) / np.maximum(valid, 1.0), np.nan)
+    return dict(valid=valid.astype(np.int64), pixel_acc=acc, mIoU=miou, iou=iou)

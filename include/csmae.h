@@ -457,6 +457,31 @@ int csmae_seg_ce(long long N, int G, int p, int K, int S, const float* pl, const
  * that read it and recomputes their softmax from pl, so every element is written exactly once, in a fixed summation order: dpl need not be cleared. */
 int csmae_seg_ce_bwd(long long N, int G, int p, int K, int S, const float* pl, const unsigned char* labels, const long long* count, const float* gscale,
                      float* dpl, void* stream);
+/* Overlay sheets, the argmax map and per-image counts of a batch (util/seg_viz.py segmentation_panels, main_segprobe.py --panel_dir / --pred_dir /
+ * --per_image; added within ABI version 7, csrc/seg_panel.hip), from the operands csmae_seg_ce scores: the same upsampling and tie rule, the upsampled
+ * logits never reach memory.  img: fp32 [N, C, S, S], normalised; mean, std: fp32 [C]; band_r, band_g, band_b: the channels shown as red, green, blue;
+ * pl: fp32 [N, G, G, K], S = G p; labels (nullable): uint8 [N, S, S], CSMAE_SEG_IGNORE = ignored; palette: uint8 [K, 3] on the device; ignore_r,
+ * ignore_g, ignore_b: the colour of an ignored pixel, bytes; a8: the overlay's alpha in 256ths, [0, 256].
+ *   out   uint8 [N][S][W][3], W = n_panes S + (n_panes - 1) gap, dense, gap bytes 255 (csmae_recon_panel's layout); needs no alignment
+ *   pred  (nullable) uint8 [N][S][S]: the argmax class of every pixel, the lowest index winning ties
+ *   stats (nullable, needs labels) int32 [N][K][3]: per image and class (intersection, label area, prediction area) over the pixels whose label
+ *         is < K; OVERWRITTEN (cleared on the stream, then added to with integer atomics), so the sum over n is the diagonal, the row sums and the
+ *         column sums of csmae_seg_ce's conf.
+ * With b = (int) min(max(255 (img std + mean), 0), 255) (csmae_recon_panel's byte), arg the argmax class and
+ * blend(b, c) = (b (256 - a8) + c a8 + 128) >> 8, pane k shows by its code pane<k> (pane<k> with k >= n_panes is ignored), at a valid pixel
+ * (label < K) | at an ignored one (label CSMAE_SEG_IGNORE, or a stray label in [K, 255)):
+ *   0 image: b | b                              1 gt: palette[label] | ignore_rgb               2 pred: palette[arg] | the same
+ *   3 gt_over: blend(b, palette[label]) | blend(b, ignore_rgb)                                   4 pred_over: blend(b, palette[arg]) | the same
+ *   5 errors: blend(b, (255, 0, 0)) where arg != label, b where it is right | blend(b, ignore_rgb)
+ * (The name has no underscore after "seg": the csmae_seg_* family is the probe's three training entry points above, and stays those three.)
+ * One kernel launch; every byte of out and pred is written exactly once; an image's bytes and counts depend on that image alone.
+ * Refused before anything is launched: a null img, mean, std, pl, palette or out; N <= 0; K outside [2, 64]; p not in {4, 8, 14, 16}; G outside
+ * [1, 4096]; S != G p; n_panes outside [1, 6]; a code outside [0, 5]; a pane 1, 3 or 5, or stats, with labels null; a band outside [0, C); gap < 0;
+ * a8 outside [0, 256]; an ignore colour outside [0, 255]; N S W 3 >= 2^31. */
+int csmae_segpanel(long long N, int C, int S, int G, int p, int K, const float* img, const float* mean, const float* std, int band_r, int band_g,
+                    int band_b, const float* pl, const unsigned char* labels, const unsigned char* palette, int ignore_r, int ignore_g, int ignore_b,
+                    int a8, int pane0, int pane1, int pane2, int pane3, int pane4, int pane5, int n_panes, int gap, unsigned char* out,
+                    unsigned char* pred, int* stats, void* stream);
 
 
 /* ---- a stream confined to a subset of the compute units (ABI version 5).  The reference overlaps DDP's bucket all-reduces and autograd's
